@@ -8,7 +8,11 @@ SSIM, i.e. BASELINE.json config 3):
 on the synthetic stand-in for media/306 (100 000 mesh-bound SH-3 splats, 802x550, the camera of
 fps_benchmark_demo.py:21-33).  Inputs are resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode train|render] [--binding fused|unfused]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode train|render] [--binding fused|unfused] [--full] [--dump-outputs DIR]
+
+A plain run sets up, runs W warm-up steps, times exactly K steps (one round; --rounds / --min-seconds add rounds) and prints
+the line.  --full adds what takes runs of its own: the per-kernel event pass and roofline record, the CPU baseline and the
+frame_streams / recorded_step / template_like legs.  --dump-outputs DIR writes what the last timed step computed (.npy).
 
 N > 1: one rank per GPU, every rank holds a replica of the splats and renders its own frames
 (frame-parallel, weak scaling); the only collective is the all-reduce of the scalar loss (RCCL over
@@ -103,12 +107,15 @@ PMC_ALIAS = {"k_render_bwd_rp": "k_render_bwd", "k_rcount": "k_count", "k_rscatt
              "k_dbucket": "k_depth_sort", "k_dscan": "k_depth_sort", "k_dscatter": "k_depth_sort", "k_dsort": "k_depth_sort", "k_qscan_glob": "k_qscan"}
 
 
-def one_step(g, cam, bg, target, t, train):
+def one_step(g, cam, bg, target, t, train, keep=None):
+    """`keep` (--dump-outputs): a dict that receives references to what the step hands its caller (no copies, no synchronisation)."""
     from gaussianavatars_amd.gaussian_renderer import l1_loss, render
 
     if g.binding is not None:
         g.select_mesh_by_timestep(t)
     pkg = render(cam, g, Pipe, bg)
+    if keep is not None:
+        keep["pkg"] = pkg
     if not train:   # forward-only workloads: a constant device scalar for the (optional) all-reduce, no reduction kernels in the timed loop
         z = _ZERO.get(pkg["render"].device)
         if z is None:
@@ -121,19 +128,59 @@ def one_step(g, cam, bg, target, t, train):
         loss = 0.8 * l1 + 0.2 * (1.0 - ss)            # lambda_dssim = 0.2 (arguments/__init__.py)
         loss.backward()
         g.update_densification_stats(pkg["viewspace_points"], pkg["radii"])
+        if keep is not None:
+            keep["loss"] = loss
         return loss.detach()
     loss = l1_loss(pkg["render"], target)
     loss.backward()
+    if keep is not None:
+        keep["loss"] = loss
     return loss.detach()
 
 
-def zero_grads(g):
+LEAVES = ("_xyz", "_features_dc", "_features_rest", "_scaling", "_rotation", "_opacity")
+
+
+def zero_grads(g, keep=None):
+    """`keep` (--dump-outputs): receives the gradients before they are dropped."""
+    if keep is not None:
+        keep["grads"] = {n: getattr(g, n).grad for n in LEAVES}
+        keep["grads"].update({"flame_" + k: v.grad for k, v in (getattr(g, "flame_param", None) or {}).items() if v.requires_grad})
     for p in (g._xyz, g._features_dc, g._features_rest, g._scaling, g._rotation, g._opacity):
         p.grad = None
     if getattr(g, "flame_param", None) is not None:
         for v in g.flame_param.values():
             if v.requires_grad:
                 v.grad = None
+
+
+DUMP_BUDGET = 64 << 20   # --dump-outputs: bytes written at most
+
+
+def dump_outputs(keep, n_splats, out_dir):
+    """--dump-outputs DIR: what the last timed step handed its caller, one float32 DIR/<name>.npy per array: the image, radii and visibility
+    mask; with a backward also the loss and the gradients of the screen-space means, the six splat leaves and the FLAME rows.  When the
+    arrays exceed DUMP_BUDGET, the per-splat ones keep a fixed, seeded sample of rows (their indices in splat_sample.npy)."""
+    pkg = keep["pkg"]
+    arrs = {"image": pkg["render"], "radii": pkg["radii"], "visibility": pkg["visibility_filter"]}
+    if "loss" in keep:
+        arrs["loss"] = keep["loss"]
+        arrs["grad_means2D"] = pkg["viewspace_points"].grad
+        arrs.update({"grad_" + n.lstrip("_"): v for n, v in keep.get("grads", {}).items()})
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in arrs.items() if v is not None}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_BUDGET:
+        rows = [k for k, a in arrs.items() if a.ndim and a.shape[0] == n_splats]
+        row_bytes = sum(arrs[k].nbytes for k in rows) // n_splats
+        m = (DUMP_BUDGET - (total - row_bytes * n_splats)) // (row_bytes + 8)
+        if m < 1:
+            raise SystemExit(f"--dump-outputs: the non-per-splat outputs alone exceed {DUMP_BUDGET >> 20} MB")
+        idx = np.sort(np.random.default_rng(0).choice(n_splats, size=min(m, n_splats), replace=False))
+        arrs.update({k: np.ascontiguousarray(arrs[k][idx]) for k in rows})
+        arrs["splat_sample"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def cpu_baseline(g, cam, bg, train, args, max_seconds=12.0):
@@ -418,9 +465,17 @@ def main():
                     help="bound workloads: the head mesh of the synthetic avatar.  ellipsoid: the stand-in of rounds 1-5 (the default line).  template_like: the same "
                          "topology with the face-area distribution and extent of the reference's head template (synthetic.head_mesh(kind=...): statistics only), "
                          "whose tiles are as deep as the avatar tools/ref_on_gpu.py stages on the real template; the default run reports it beside `value`")
-    ap.add_argument("--no-template-like", action="store_true", help="default N=1 run: skip the template_like leg")
-    ap.add_argument("--rounds", type=int, default=3, help="minimum number of timed rounds of --steps steps each (the median round is reported)")
-    ap.add_argument("--min-seconds", type=float, default=3.0, help="minimum total timed duration: rounds are added until it is reached")
+    ap.add_argument("--no-template-like", action="store_true", help="--full N=1 run: skip the template_like leg")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure as well: the per-kernel event pass and the roofline record, the L1+SSIM loss timing "
+                         "(--workload train), the CPU baseline, and the frame_streams / recorded_step / template_like legs (child processes).  "
+                         "Off by default: a plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (image, radii, visibility; with a backward the loss and "
+                         "the gradients) as DIR/<name>.npy in float32, at most 64 MB (a fixed, seeded sample of splat rows beyond that)")
+    ap.add_argument("--rounds", type=int, default=1,
+                    help="minimum number of timed rounds of --steps steps each (the median round is reported); the default, one round, times exactly --steps steps")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="minimum total timed duration: rounds are added until it is reached (default 0: --rounds alone)")
     ap.add_argument("--backend", choices=["nccl", "gloo", "gloo_gpu"], default="nccl",
                     help="nccl (= RCCL): the measured path.  gloo: DRY run of the multi-rank plumbing on CPU -- a few hundred splats, composed-torch "
                          "binding, the rasterizer stubbed at its autograd Function; the line is marked as such and is not a measurement.  gloo_gpu: the REAL step "
@@ -452,6 +507,10 @@ def main():
                          "backend's all-reduce, so that a one-GPU box EXECUTES the RCCL path the N-GPU run takes (tests/test_rccl_gpu.py); the line "
                          "says so in config.parallelism.  Not the default: at N = 1 the reference-shaped run has no collective")
     args = ap.parse_args()
+    if not args.full:   # a plain run: the headline figure only
+        args.no_cpu_baseline, args.no_kernel_profile, args.no_template_like, args.frame_streams = True, True, True, 0
+    if args.dump_outputs and (args.graph or args.streams > 1):
+        raise SystemExit("--dump-outputs covers the eager frame loop (the recorded lanes keep their outputs in static buffers)")
     SCENE = args.scene
     SPATIAL_SORT = not args.no_spatial_sort and os.environ.get("GAA_SPATIAL_SORT", "1") != "0"
     if args.workload == "cfg3" and args.mode == "render":
@@ -530,11 +589,13 @@ def main():
 
         GR.l1_loss = lambda a, b: (a - b).abs().mean()   # one_step imports it from there
 
+    last = {} if args.dump_outputs else None   # --dump-outputs: references to what the latest step returned
+
     def step_fn(t):
         with torch.set_grad_enabled(train):
-            return one_step(g, cam, bg, target, t, train)
+            return one_step(g, cam, bg, target, t, train, keep=last)
 
-    run = make_runner(step_fn, my_frames, dist, device, post_step=(lambda: zero_grads(g)) if train else None)
+    run = make_runner(step_fn, my_frames, dist, device, post_step=(lambda: zero_grads(g, keep=last)) if train else None)
     run_eager, graphed, lanes = run, None, []
     # the instrumented pass further down runs on rank 0 ONLY: its runner must not contain the per-step all-reduce (a collective entered by one rank of N pairs
     # with whatever the other ranks enter next -- their barrier -- and the run hangs; found in round 5, the N > 1 path on RCCL had never executed before)
@@ -691,6 +752,9 @@ def main():
     rounds = timed_rounds(run, fence, args.steps, args.warmup, dist, device, min_rounds=args.rounds, min_seconds=args.min_seconds, max_rounds=100_000)   # (--min-seconds is the stopping rule; round 3 capped it at 256 rounds)
     elapsed = float(np.median(rounds))   # the median round: exactly args.steps steps
     wait_ms, waits = _lib.gsr_wait_stats()
+    if last is not None and rank == 0:   # before any later pass reuses step_fn
+        dump_outputs(last, int(g._xyz.shape[0]), args.dump_outputs)
+        last = None
     info = {"binning_path": 0} if dry else R.last_forward_info()
     if graphed is not None:
         for ln in lanes:
@@ -780,7 +844,7 @@ def main():
     if rank == 0 and world == 1 and not args.graph and not dry and args.scene == "ellipsoid" and args.workload != "cfg5" and not args.no_template_like:
         import subprocess
 
-        cmd = [sys.executable, os.path.abspath(__file__), "--scene", "template_like", "--frame-streams", "0", "--no-cpu-baseline", "--workload", args.workload,
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--scene", "template_like", "--frame-streams", "0", "--no-cpu-baseline", "--workload", args.workload,
                "--steps", str(args.steps), "--warmup", str(args.warmup), "--rounds", str(args.rounds), "--min-seconds", str(min(args.min_seconds, 1.5)),
                "--splats", str(args.splats), "--width", str(args.width), "--height", str(args.height), "--frames", str(args.frames), "--binding", args.binding] + (
                    ["--no-pin"] if args.no_pin else []) + ([] if SPATIAL_SORT else ["--no-spatial-sort"])
@@ -873,7 +937,7 @@ def main():
         pmc, pmc_raw = {}, {}
         pmc_tag = {"cfg5": "cfg5", "cfg4": "cfg4", "cfg3": "cfg3", "cfg2": "cfg3", "train": "cfg3"}.get(args.workload)   # (train: cfg3's rasterizer kernels)
         import glob
-        cands = sorted(glob.glob(os.path.join(ROOT, "profiles", f"r*_{pmc_tag}_pmc_fetch_write_per_launch.json"))) if pmc_tag else []
+        cands = sorted(glob.glob(os.path.join(ROOT, "profiles", f"r*_{pmc_tag}_pmc_fetch_write_per_launch.json"))) if pmc_tag and per_kernel else []
         pmc_path = cands[-1] if cands else ""   # the newest committed PMC summary of this workload
         pmc_stale = None
         if pmc_path:   # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this same command (profiles/README.md)
@@ -981,7 +1045,7 @@ def main():
                                    f"not the latency of one frame)" if len(lanes) > 1 else "")),
             },
             # every timed round is exactly `steps` steps (barrier + device sync on both sides, MAX over ranks); value = median round
-            # (the per-round list is thinned to at most 64 evenly spaced rounds: with --min-seconds uncapped a default run has ~500 rounds, and the
+            # (the per-round list is thinned to at most 64 evenly spaced rounds: a long --min-seconds gives hundreds of rounds, and the
             #  line is read by tools that keep a bounded tail of stdout; n / min / p10 / max are over ALL rounds)
             "rounds": {"n": len(rounds), "frames_per_s": [round(n_gpus * args.steps / rounds[int(i)], 2) for i in np.linspace(0, len(rounds) - 1, min(len(rounds), 64))],
                        "min": round(n_gpus * args.steps / max(rounds), 2), "p10": round(n_gpus * args.steps / float(np.percentile(rounds, 90)), 2),

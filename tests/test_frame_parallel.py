@@ -261,6 +261,50 @@ def test_two_ranks_of_two_lanes_dry():
     assert torch.equal(a._xyz, g._xyz) and torch.equal(b._xyz, g._xyz)
 
 
+def test_bench_plain_run_times_exactly_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times exactly --steps steps in one round and carries none of the passes that take runs of their own;
+    --dump-outputs writes what the last timed step computed as float32 .npy files, the same bits from run to run.  Dry path (--backend gloo)."""
+    import numpy as np
+
+    outs = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        r, lines = _bench("--backend", "gloo", "--steps", "3", "--warmup", "1", "--frames", "5", "--dump-outputs", str(d))
+        assert r.returncode == 0, r.stdout + r.stderr
+        assert len(lines) == 1
+        out = lines[0]
+        assert out["steps"] == 3 and out["rounds"]["n"] == 1
+        assert abs(3 * out["ms_per_step"] - 1e3 * out["rounds"]["timed_seconds"]) <= 0.01 * 3 * out["ms_per_step"] + 0.1
+        assert out["roofline"] is None and out["cpu_baseline"] is None and out["frame_streams"] is None and out["template_like"] is None
+        files = {p.name: np.load(p) for p in d.iterdir()}
+        assert {"image.npy", "loss.npy", "radii.npy", "visibility.npy", "grad_xyz.npy", "grad_means2D.npy", "grad_flame_expr.npy"} <= set(files)
+        assert all(a.dtype == np.float32 for a in files.values())
+        assert files["image.npy"].shape == (3, 48, 64) and files["loss.npy"].shape == ()
+        outs.append(files)
+    assert outs[0].keys() == outs[1].keys() and all(np.array_equal(outs[0][k], outs[1][k]) for k in outs[0])
+
+
+def test_bench_dump_outputs_samples_splat_rows_beyond_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+
+    import bench
+
+    n = 1000
+    pts = torch.zeros(n, 3, requires_grad=True)
+    pts.grad = torch.arange(3 * n, dtype=torch.float32).reshape(n, 3)
+    keep = {"pkg": {"render": torch.rand(3, 8, 8), "radii": torch.arange(n, dtype=torch.int32), "visibility_filter": torch.ones(n, dtype=torch.bool),
+                    "viewspace_points": pts},
+            "loss": torch.tensor(0.5), "grads": {"_xyz": torch.ones(n, 3)}}
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 8000)
+    bench.dump_outputs(keep, n, str(tmp_path))
+    files = {p.stem: np.load(p) for p in tmp_path.iterdir()}
+    assert sum(a.nbytes for a in files.values()) <= 8000
+    idx = files["splat_sample"].astype(np.int64)
+    assert len(idx) > 0 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(files["radii"], idx.astype(np.float32)) and np.array_equal(files["grad_means2D"], pts.grad.numpy()[idx])
+    assert files["image"].shape == (3, 8, 8) and files["grad_xyz"].shape == (len(idx), 3)
+
+
 def test_bench_gpus_flag_refuses_what_it_cannot_deliver():
     if torch.cuda.is_available() and torch.cuda.device_count() >= 2:
         pytest.skip("two GPUs present: the refusal does not apply")

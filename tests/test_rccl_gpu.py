@@ -97,7 +97,7 @@ def test_bench_under_torch_distributed_run_on_nccl_at_one_gpu():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "3", "--dist-at-1", "--no-cpu-baseline",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "10", "--warmup", "3", "--dist-at-1", "--no-cpu-baseline",
            "--frame-streams", "0", "--min-seconds", "0.3", "--frames", "16"]
     r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=270)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -118,7 +118,7 @@ def test_two_ranks_sharing_the_gpu_run_the_multi_rank_control_flow():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo_gpu", "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--frame-streams", "0",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo_gpu", "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--frame-streams", "0",
            "--min-seconds", "0.3", "--frames", "16", "--no-pin"]
     r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=270)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

@@ -13,6 +13,7 @@ the rasterizer Function (test infrastructure), and GAA_BINDING_IMPL=unfused keep
 -- argument parsing, safe_state, FlameGaussianModel(), load_ply, the three timed rounds of select_mesh_by_timestep + render, the FPS
 report -- is the reference's code.  On an MI355X the same command without those two stand-ins is the GPU run."""
 import os
+import shutil
 import subprocess
 import sys
 import textwrap
@@ -196,6 +197,11 @@ def test_ref_on_gpu_stage_puts_an_ignored_scratch_copy_with_generated_assets(tmp
         assert os.path.exists(os.path.join(ref, "flame_model", "assets", "flame", asset)), asset
     assert os.path.exists(os.path.join(scratch, "avatar", "point_cloud.ply")) and os.path.exists(os.path.join(scratch, "avatar", "flame_param.npz"))
     assert os.path.exists(os.path.join(scratch, "data", "transforms_train.json")) and os.path.exists(os.path.join(scratch, "STAGED.json"))
-    # the real location is git-ignored (never committed): `git check-ignore` knows the rule
-    r = subprocess.run(["git", "check-ignore", "-q", "_ref_scratch/reference/train.py"], cwd=ROOT)
+    # the real location is git-ignored (never committed): `git check-ignore` knows the rule.  Asked of a fresh repository that holds only this
+    # checkout's .gitignore, so that the answer does not depend on whether the checkout carries its .git (an exported tree has none)
+    probe = tmp_path / "ignore_probe"
+    probe.mkdir()
+    shutil.copyfile(os.path.join(ROOT, ".gitignore"), probe / ".gitignore")
+    subprocess.run(["git", "init", "-q"], cwd=probe, check=True)
+    r = subprocess.run(["git", "-c", "core.excludesFile=/dev/null", "check-ignore", "-q", "_ref_scratch/reference/train.py"], cwd=probe)
     assert r.returncode == 0
