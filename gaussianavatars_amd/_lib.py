@@ -332,3 +332,43 @@ def gab_error() -> str:
 
 def gsr_error() -> str:
     return gsr().gsr_last_error().decode("utf-8", "replace")
+
+
+# ------------------------------------------------------------------------------------------------
+# libgmr_hip.so : the mesh overlay's triangle rasterizer and antialias (include/gmr.h).  Loaded only by mesh_raster.py:
+# the splat path never maps it.
+# ------------------------------------------------------------------------------------------------
+GMR_LIB_PATH = os.path.join(_HERE, "libgmr_hip.so")
+GMR_SYMBOLS = {
+    "gmr_abi_version": (C.c_int, []),
+    "gmr_last_error": (C.c_char_p, []),
+    "gmr_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "gmr_rasterize": (C.c_int, [C.c_int32] * 5 + [_P, _P, _P, _P, _P]),
+    "gmr_antialias": (C.c_int, [C.c_int32] * 6 + [_P] * 7),
+}
+GMR_ABI_VERSION = 1
+GMR_MAX_TRIANGLES = (1 << 24) - 1   # include/gmr.h: triangle_id + 1 is stored as an exact float
+
+_gmr = None
+
+
+def gmr():
+    """The mesh rasterizer library; raises (never falls back) when it is not built."""
+    global _gmr
+    if _gmr is None:
+        if not os.path.exists(GMR_LIB_PATH):
+            raise RuntimeError(f"{GMR_LIB_PATH} is missing: run __graft_entry__.build() (hipcc, gfx950).  There is no CPU fallback.")
+        _torch_first()
+        lib = C.CDLL(GMR_LIB_PATH)
+        for name, (res, args) in GMR_SYMBOLS.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.gmr_abi_version() != GMR_ABI_VERSION:
+            raise RuntimeError(f"gmr ABI version {lib.gmr_abi_version()} != {GMR_ABI_VERSION}")
+        _gmr = lib
+    return _gmr
+
+
+def gmr_error() -> str:
+    return gmr().gmr_last_error().decode("utf-8", "replace")

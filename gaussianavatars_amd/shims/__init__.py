@@ -4,7 +4,7 @@ MI355X box (CUDA-only builds or un-vendored submodules -- SURVEY.md Appendix B /
     roma                 4 quaternion functions        scene/gaussian_model.py:21, scene/flame_gaussian_model.py:18
     plyfile              PlyData / PlyElement subset   scene/gaussian_model.py:19, scene/dataset_readers.py:23
     simple_knn._C        distCUDA2                     scene/gaussian_model.py:23 (init of un-bound models only)
-    nvdiffrast.torch     contexts construct, use raises  mesh_renderer/__init__.py:10 (debug overlay only)
+    nvdiffrast.torch     rasterize / antialias (HIP)   mesh_renderer/__init__.py:10 (mesh overlay: gaussianavatars_amd.mesh_raster)
     dearpygui.dearpygui  import-time stub              utils/viewer_utils.py:17 (fps_benchmark_demo.py needs OrbitCamera only)
     tyro                 import-time stub              viewers
     iopath.common.file_io  PathManager.open            utils/pytorch3d_load_obj.py:47 (FlameHead's template OBJ)
