@@ -372,3 +372,71 @@ def gmr():
 
 def gmr_error() -> str:
     return gmr().gmr_last_error().decode("utf-8", "replace")
+
+
+# ------------------------------------------------------------------------------------------------
+# libgop_hip.so : the fused Adam step (include/gop.h).  Loaded only by optim.py, at the first step on device tensors.
+# ------------------------------------------------------------------------------------------------
+GOP_LIB_PATH = os.path.join(_HERE, "libgop_hip.so")
+GOP_ABI_VERSION = 1
+GOP_MAX_TENSORS = 32   # include/gop.h: tensors per launch
+GOP_SLAB = 2048        # include/gop.h: elements per workgroup
+
+
+class GopAdamTensor(C.Structure):
+    """include/gop.h: GopAdamTensor"""
+    _fields_ = [("param", _P), ("grad", _P), ("exp_avg", _P), ("exp_avg_sq", _P), ("n", C.c_int64), ("step_size", C.c_float),
+                ("bias_correction2_sqrt", C.c_float)]
+
+
+GOP_SYMBOLS = {
+    "gop_abi_version": (C.c_int, []),
+    "gop_last_error": (C.c_char_p, []),
+    "gop_adam_step": (C.c_int, [C.c_int32, C.POINTER(GopAdamTensor), C.c_float, C.c_float, C.c_float, _P]),
+    "gop_adam_step_ex": (C.c_int, [C.c_int32, C.POINTER(GopAdamTensor)] + [C.c_float] * 5 + [_P]),
+    "gop_profile_enable": (C.c_int, [C.c_int]),
+    "gop_profile_collect": (C.c_int, []),
+    "gop_profile_entry": (C.c_int, [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "gop_profile_reset": (C.c_int, []),
+}
+
+_gop = None
+
+
+def gop():
+    """The optimizer library; raises (never falls back) when it is not built."""
+    global _gop
+    if _gop is None:
+        if not os.path.exists(GOP_LIB_PATH):
+            raise RuntimeError(f"{GOP_LIB_PATH} is missing: run __graft_entry__.build() (hipcc, gfx950).  There is no CPU fallback.")
+        _torch_first()
+        lib = C.CDLL(GOP_LIB_PATH)
+        for name, (res, args) in GOP_SYMBOLS.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.gop_abi_version() != GOP_ABI_VERSION:
+            raise RuntimeError(f"gop ABI version {lib.gop_abi_version()} != {GOP_ABI_VERSION}")
+        _gop = lib
+    return _gop
+
+
+def gop_error() -> str:
+    return gop().gop_last_error().decode("utf-8", "replace")
+
+
+def gop_profile_enable(on: bool) -> None:
+    """Event pairs around every launch of libgop (include/gop.h: gop_profile_*), from an empty table."""
+    gop().gop_profile_enable(1 if on else 0)
+    if on:
+        gop().gop_profile_reset()
+
+
+def gop_profile_read() -> dict:
+    """{kernel name: (total_ms, launches)} of libgop's launches since gop_profile_enable(True)."""
+    out = {}
+    for i in range(gop().gop_profile_collect()):
+        name, ms, k = C.c_char_p(), C.c_double(), C.c_int64()
+        if gop().gop_profile_entry(i, C.byref(name), C.byref(ms), C.byref(k)) == 0:
+            out[name.value.decode()] = (ms.value, k.value)
+    return out

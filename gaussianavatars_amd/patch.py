@@ -294,7 +294,7 @@ def unpatch_classes(*classes) -> None:
             setattr(cls, name, orig)
             del _ORIG[(cls, name)]
     for cls in classes:
-        for flag in ("_gaa_patched", "_gaa_patched_flame", "_gaa_patched_head", "_gaa_patched_base", "_gaa_patched_stats"):
+        for flag in ("_gaa_patched", "_gaa_patched_flame", "_gaa_patched_head", "_gaa_patched_base", "_gaa_patched_stats", "_gaa_patched_optimizer"):
             if flag in cls.__dict__:
                 delattr(cls, flag)
         if isinstance(cls.__dict__.get("get_features_split"), property) and cls.__dict__["get_features_split"].fget is _get_features_split:
@@ -316,8 +316,10 @@ def patch_reference(reference_root: str | None = None, fast_render: bool = True,
        device 1 instead of a one-element fill launch.
     6. (GAA_FUSED_LOSS=0 opts out) patch_loss_and_stats: `utils.loss_utils.l1_loss` / `ssim` and `GaussianModel.add_densification_stats`
        -> the fused kernels of include/gls.h (train.py:131-132,198 unchanged).
-    Returns {'shims': [...], 'classes': [...], 'render': bool, 'pinned_cpus': [...] | None, 'backward_seed': bool, 'loss': [...]}.  Call it
-    before the entry script imports `render`."""
+    7. (GAA_FUSED_ADAM=0 opts out) patch_optimizer: the torch.optim.Adam that `training_setup` builds becomes an optim.FusedAdam, so
+       train.py:209's `gaussians.optimizer.step()` is one launch of include/gop.h.
+    Returns {'shims': [...], 'classes': [...], 'render': bool, 'pinned_cpus': [...] | None, 'backward_seed': bool, 'loss': [...],
+    'optimizer': [...]}.  Call it before the entry script imports `render`."""
     from . import shims
 
     repo_root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -353,8 +355,44 @@ def patch_reference(reference_root: str | None = None, fast_render: bool = True,
         install_backward_seed()
         seeded = True
     fused_loss = patch_loss_and_stats(gm.GaussianModel) if os.environ.get("GAA_FUSED_LOSS", "1") != "0" else []
+    fused_adam = patch_optimizer(gm.GaussianModel, fgm.FlameGaussianModel) if os.environ.get("GAA_FUSED_ADAM", "1") != "0" else []
     return dict(shims=served, classes=[gm.GaussianModel, fgm.FlameGaussianModel, flame.FlameHead], render=did_render, pinned_cpus=pinned,
-                backward_seed=seeded, loss=fused_loss)
+                backward_seed=seeded, loss=fused_loss, optimizer=fused_adam)
+
+
+def patch_optimizer(gaussian_model_cls, flame_gaussian_model_cls=None) -> list:
+    """The optimizer step behind the zero-edit boundary: wraps `training_setup` of the classes that define it (scene/gaussian_model.py:208-226,
+    scene/flame_gaussian_model.py:174-208) so that, after the original has returned, `self.optimizer = optim.adopt(self.optimizer)`: the very
+    torch.optim.Adam object the reference built -- its six named groups, and the three FlameGaussianModel adds with add_param_group -- steps
+    through include/gop.h (optim.FusedAdam: same state, same state_dict, torch's own step outside the kernel's domain, e.g. on CPU tensors).
+    `restore()` goes through `training_setup` (scene/gaussian_model.py:96) and is covered by the same wrap.  Idempotent; undone by
+    unpatch_classes; GAA_FUSED_ADAM=0 keeps patch_reference() from calling it.  Returns the names rebound.
+
+    This package's own mirror classes (gaussian_model.py) have no `training_setup`: their users construct `optim.FusedAdam` directly."""
+    from . import optim
+
+    done = []
+    for cls in (gaussian_model_cls, flame_gaussian_model_cls):
+        if cls is None or "training_setup" not in cls.__dict__ or cls.__dict__.get("_gaa_patched_optimizer", False):
+            continue
+        orig = cls.__dict__["training_setup"]
+        _ORIG[(cls, "training_setup")] = orig
+        cls.training_setup = _make_training_setup(orig, optim)
+        cls._gaa_patched_optimizer = True
+        done.append(f"{cls.__name__}.training_setup")
+    return done
+
+
+def _make_training_setup(orig, optim):
+    def training_setup(self, *a, **k):
+        out = orig(self, *a, **k)
+        if getattr(self, "optimizer", None) is not None:
+            self.optimizer = optim.adopt(self.optimizer)
+        return out
+
+    training_setup.__name__ = getattr(orig, "__name__", "training_setup")
+    training_setup.__doc__ = orig.__doc__
+    return training_setup
 
 
 def patch_loss_and_stats(gaussian_model_cls=None, loss_utils=None) -> list:
