@@ -440,3 +440,65 @@ def gop_profile_read() -> dict:
         if gop().gop_profile_entry(i, C.byref(name), C.byref(ms), C.byref(k)) == 0:
             out[name.value.decode()] = (ms.value, k.value)
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# libgrl_hip.so : the fused splat regularisers (include/grl.h).  Loaded only by loss.splat_regularizers, at the first call on device tensors.
+# ------------------------------------------------------------------------------------------------
+GRL_LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
+GRL_ABI_VERSION = 1
+GRL_SLAB = 1024               # include/grl.h: splats per workgroup
+GRL_MAX_SPLATS = 1 << 24      # include/grl.h: P must stay below this (the count is an exact float)
+
+GRL_SYMBOLS = {
+    "grl_abi_version": (C.c_int, []),
+    "grl_last_error": (C.c_char_p, []),
+    "grl_scratch_bytes": (C.c_int64, [C.c_int32]),
+    "grl_forward": (C.c_int, [C.c_int32, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P]),
+    "grl_backward": (C.c_int, [C.c_int32, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P]),
+    "grl_profile_enable": (C.c_int, [C.c_int]),
+    "grl_profile_collect": (C.c_int, []),
+    "grl_profile_entry": (C.c_int, [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "grl_profile_reset": (C.c_int, []),
+}
+
+_grl = None
+
+
+def grl():
+    """The regulariser library; raises (never falls back) when it is not built."""
+    global _grl
+    if _grl is None:
+        if not os.path.exists(GRL_LIB_PATH):
+            raise RuntimeError(f"{GRL_LIB_PATH} is missing: run __graft_entry__.build() (hipcc, gfx950).  There is no CPU fallback.")
+        _torch_first()
+        lib = C.CDLL(GRL_LIB_PATH)
+        for name, (res, args) in GRL_SYMBOLS.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.grl_abi_version() != GRL_ABI_VERSION:
+            raise RuntimeError(f"grl ABI version {lib.grl_abi_version()} != {GRL_ABI_VERSION}")
+        _grl = lib
+    return _grl
+
+
+def grl_error() -> str:
+    return grl().grl_last_error().decode("utf-8", "replace")
+
+
+def grl_profile_enable(on: bool) -> None:
+    """Event pairs around every launch of libgrl (include/grl.h: grl_profile_*), from an empty table."""
+    grl().grl_profile_enable(1 if on else 0)
+    if on:
+        grl().grl_profile_reset()
+
+
+def grl_profile_read() -> dict:
+    """{kernel name: (total_ms, launches)} of libgrl's launches since grl_profile_enable(True)."""
+    out = {}
+    for i in range(grl().grl_profile_collect()):
+        name, ms, k = C.c_char_p(), C.c_double(), C.c_int64()
+        if grl().grl_profile_entry(i, C.byref(name), C.byref(ms), C.byref(k)) == 0:
+            out[name.value.decode()] = (ms.value, k.value)
+    return out

@@ -4,6 +4,10 @@ after backward (train.py:197-198, scene/gaussian_model.py:517-519) on the fused 
 `l1_loss(a, b)` and `ssim(img1, img2)` keep the reference's names, arguments and return values so
 train.py:131-132 reads unchanged; `l1_ssim(image, gt)` returns both from one pass over the pair (what a training
 step should call).  There is no torch fallback: a CPU tensor or a missing library raises.
+
+`regularization_losses(gaussians, visibility_filter, opt)` is the drop-in for the two splat regularisers of a mesh-bound run
+(train.py:135-146) on the fused kernels of include/grl.h; `splat_regularizers` is the pair of means behind it.  Inputs outside those
+kernels' domain evaluate the reference's own composed expressions (they are the definition; a missing library still raises).
 """
 from __future__ import annotations
 
@@ -376,3 +380,128 @@ def densification_stats(radii: torch.Tensor, viewspace_grad: torch.Tensor, max_r
     dev = radii.device
     _launch(dev, "gls_densification_stats", _lib.gls().gls_densification_stats, P, _p(radii.contiguous()), _p(vg), _p(max_radii2D), _p(xyz_gradient_accum), _p(denom),
                                               _stream(radii.device))
+
+
+# ---- the two splat regularisers of a mesh-bound run (train.py:134-146) on the fused kernels of include/grl.h -------------------------------
+def _composed_regularizers(xyz, log_scaling, visibility_filter, threshold_xyz, threshold_scale):
+    """train.py:139 and :146 as the reference writes them (metric_xyz = metric_scale = False), without their lambdas."""
+    xyz_mean = torch.nn.functional.relu(xyz[visibility_filter].norm(dim=1) - threshold_xyz).mean()
+    scale_mean = torch.nn.functional.relu(torch.exp(log_scaling[visibility_filter]) - threshold_scale).norm(dim=1).mean()
+    return xyz_mean, scale_mean
+
+
+_REG_SCRATCH = {}   # (device index, raw stream) -> zeroed-once scratch of include/grl.h; never shared between two streams
+
+
+def _reg_scratch(dev, stream, nbytes):
+    """The (device, stream)'s scratch, grown when a larger model arrives.  The kernel leaves it ready for the next call on the same stream, so
+    it is zeroed only here.  Under stream capture nothing is cached: a scratch made there lives in that graph's private pool, and its
+    zero-fill is recorded with it."""
+    key = (dev.index, stream)
+    held = _REG_SCRATCH.get(key)
+    if held is not None and held.numel() >= nbytes:
+        return held
+    held = torch.zeros(max(nbytes, 4096), dtype=torch.uint8, device=dev)
+    if not torch.cuda.is_current_stream_capturing():
+        _REG_SCRATCH[key] = held
+    return held
+
+
+def _reg_launch(dev, what, fn, *args):
+    with _lib.on_device(dev):
+        rc = fn(*args)
+    if rc != 0:
+        raise RuntimeError(f"{what} failed ({rc}): {_lib.grl_error()}")
+
+
+class _SplatRegularizers(torch.autograd.Function):
+    """(P,3) x (P,3) x (P,) bool -> (xyz_mean, scale_mean): one launch forward, one backward that recomputes from the inputs (include/grl.h).
+    The two scalars are views of the node's 4-float result made inside forward, like _L1Ssim's."""
+
+    @staticmethod
+    def forward(ctx, xyz, log_scaling, visible, threshold_xyz, threshold_scale):
+        ctx.set_materialize_grads(False)
+        lib = _lib.grl()
+        dev = xyz.device
+        P = xyz.shape[0]
+        stream = _stream(dev)
+        out = torch.empty(4, dtype=torch.float32, device=dev)
+        scratch = _reg_scratch(dev, stream, int(lib.grl_scratch_bytes(P)))
+        _reg_launch(dev, "grl_forward", lib.grl_forward, P, _p(xyz), _p(log_scaling), _p(visible), threshold_xyz, threshold_scale, _p(out), _p(scratch), stream)
+        ctx.save_for_backward(xyz, log_scaling, visible)
+        ctx.out, ctx.thresholds = out, (threshold_xyz, threshold_scale)
+        return out[0], out[1]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_xyz, g_scale):
+        xyz, log_scaling, visible = ctx.saved_tensors
+        want_x = ctx.needs_input_grad[0] and g_xyz is not None
+        want_s = ctx.needs_input_grad[1] and g_scale is not None
+        if not (want_x or want_s):
+            return None, None, None, None, None
+        lib = _lib.grl()
+        dev = xyz.device
+        gx = g_xyz.to(torch.float32).contiguous() if want_x else None
+        gs = g_scale.to(torch.float32).contiguous() if want_s else None
+        d_xyz = torch.empty_like(xyz) if want_x else None
+        d_ls = torch.empty_like(log_scaling) if want_s else None
+        _reg_launch(dev, "grl_backward", lib.grl_backward, xyz.shape[0], _p(xyz), _p(log_scaling), _p(visible), ctx.thresholds[0], ctx.thresholds[1],
+                    _p(ctx.out), _p(gx), _p(gs), _p(d_xyz), _p(d_ls), _stream(dev))
+        return d_xyz, d_ls, None, None, None
+
+
+def splat_regularizers(xyz: torch.Tensor, log_scaling: torch.Tensor, visibility_filter: torch.Tensor, threshold_xyz: float, threshold_scale: float):
+    """-> (xyz_mean, scale_mean), the two means of train.py:139 and :146 before their lambdas:
+
+        xyz_mean   = relu(xyz[visibility_filter].norm(dim=1) - threshold_xyz).mean()
+        scale_mean = relu(exp(log_scaling[visibility_filter]) - threshold_scale).norm(dim=1).mean()
+
+    from ONE launch (and one more in the backward, for the gradients autograd asks for), with no mask gather and no host wait: include/grl.h.
+    The kernels take float32 (P,3) device tensors, a bool (P,) filter on the same device and P < 2^24; non-contiguous inputs are made contiguous.
+    Anything else -- CPU tensors, another dtype, an index list as the filter -- evaluates the two expressions above in composed torch and returns
+    the same tuple.  No visible splat gives NaN, NaN (the mean of an empty tensor) and zero gradients."""
+    ok = (xyz.is_cuda and log_scaling.is_cuda and visibility_filter.is_cuda and xyz.device == log_scaling.device == visibility_filter.device
+          and xyz.dtype is torch.float32 and log_scaling.dtype is torch.float32 and visibility_filter.dtype is torch.bool
+          and xyz.dim() == 2 and xyz.shape[1] == 3 and log_scaling.shape == xyz.shape and visibility_filter.shape == (xyz.shape[0],)
+          and xyz.shape[0] < _lib.GRL_MAX_SPLATS)
+    if not ok:
+        return _composed_regularizers(xyz, log_scaling, visibility_filter, threshold_xyz, threshold_scale)
+    return _SplatRegularizers.apply(xyz.contiguous(), log_scaling.contiguous(), visibility_filter.contiguous(), float(threshold_xyz), float(threshold_scale))
+
+
+def regularization_losses(gaussians, visibility_filter, opt) -> dict:
+    """The drop-in for train.py:135-146: `losses.update(regularization_losses(gaussians, visibility_filter, opt))`.
+
+    -> {'xyz': ...} plus 'scale' when opt.lambda_scale != 0, each already multiplied by its lambda; {} for an unbound model
+    (gaussians.binding is None: the `if` of train.py:134).  With opt.metric_xyz and opt.metric_scale both false -- the defaults of
+    arguments/__init__.py -- both terms come from one fused call of splat_regularizers.  A metric flag sends ITS term to the reference's
+    composed-torch line: the metric forms multiply by face_scaling[binding] and so send gradient into the face frames, which needs a per-face
+    reduction that is deliberately not part of the fused kernels.  GAA_FUSED_REG=0 forces composed torch for both terms.  The loop's other
+    regularisers (dy_off, lap, dynamic_offset_std: zero weight by default) stay the script's own lines."""
+    if gaussians.binding is None:
+        return {}
+    F = torch.nn.functional
+    want_scale = opt.lambda_scale != 0
+    fused = os.environ.get("GAA_FUSED_REG", "1") != "0"
+    fuse_xyz = fused and not opt.metric_xyz
+    fuse_scale = fused and want_scale and not opt.metric_scale
+    losses = {}
+    xyz_mean = scale_mean = None
+    if fuse_xyz or fuse_scale:   # one call; a term that is not taken from it gets no upstream gradient and costs the backward nothing
+        fx, fs = splat_regularizers(gaussians._xyz, gaussians._scaling, visibility_filter, opt.threshold_xyz, opt.threshold_scale)
+        xyz_mean, scale_mean = (fx if fuse_xyz else None), (fs if fuse_scale else None)
+    if xyz_mean is None:
+        if opt.metric_xyz:
+            xyz_mean = F.relu((gaussians._xyz * gaussians.face_scaling[gaussians.binding])[visibility_filter] - opt.threshold_xyz).norm(dim=1).mean()
+        else:
+            xyz_mean = F.relu(gaussians._xyz[visibility_filter].norm(dim=1) - opt.threshold_xyz).mean()
+    losses["xyz"] = xyz_mean * opt.lambda_xyz
+    if want_scale:
+        if scale_mean is None:
+            if opt.metric_scale:
+                scale_mean = F.relu(gaussians.get_scaling[visibility_filter] - opt.threshold_scale).norm(dim=1).mean()
+            else:
+                scale_mean = F.relu(torch.exp(gaussians._scaling[visibility_filter]) - opt.threshold_scale).norm(dim=1).mean()
+        losses["scale"] = scale_mean * opt.lambda_scale
+    return losses
