@@ -8,6 +8,8 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from functools import partial
+from typing import NamedTuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -47,9 +49,100 @@ def on_device(dev):
 
 
 _ONE_DEVICE = None   # a process that sees one GPU never switches devices
-# GSR_LIB overrides the library file (kernel experiments build variants side by side: tools/exp_build.sh); the product default is
-# the in-tree build.  An override that does not exist is an error, never a fallback.
-GSR_LIB_PATH = os.environ.get("GSR_LIB") or os.path.join(_HERE, "libgsr_hip.so")
+
+
+# ---- the loader: one description per library, one _load() for all of them -------------------------------------------
+class LibSpec(NamedTuple):
+    """What _load() needs to map lib<tag>_hip.so and hold it to include/<tag>.h."""
+    tag: str        # prefix of every export: <tag>_abi_version, <tag>_last_error, ...
+    path: str
+    symbols: dict   # every symbol include/<tag>.h declares -> (restype, argtypes)
+    abi: int        # <TAG>_ABI_VERSION of the header this file mirrors
+
+
+#: tag -> LibSpec of every HIP library the package ships; the module-level function of the same name (gsr(), gab(), ...) loads it
+LIBS = {}
+
+
+def _lib_path(tag, env=None):
+    """The in-tree build of a library, or the file the environment variable `env` names (kernel experiments build variants side by side:
+    tools/exp_build.sh).  An override that does not exist is an error, never a fallback."""
+    return (env and os.environ.get(env)) or os.path.join(_HERE, f"lib{tag}_hip.so")
+
+
+def _torch_first():
+    """The libraries take raw device pointers of torch tensors and launch on torch's streams, so they have to share torch's HIP
+    runtime: torch is imported before the first library is mapped.  (Mapped first -- e.g. build() followed by smoke() in one
+    process -- they pull in /opt/rocm's libamdhip64 ahead of the copy torch ships, and the first runtime call that needs the
+    device fails with 'no ROCm-capable device is detected'.)"""
+    import torch  # noqa: F401
+
+
+def _load(spec):
+    """Map one library and check it against its description; raises (never falls back) when it is not built, lacks a symbol or is stale.
+    The caller keeps the handle: gsr() ... grl() below each cache theirs in a module global, so their warm path is a global load and a test."""
+    if not os.path.exists(spec.path):
+        raise RuntimeError(
+            f"{spec.path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950).  There is no CPU fallback."
+        )
+    _torch_first()
+    lib = C.CDLL(spec.path)
+    for name, (res, args) in spec.symbols.items():
+        fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
+        fn.restype = res
+        fn.argtypes = args
+    have = getattr(lib, spec.tag + "_abi_version")()
+    if have != spec.abi:
+        raise RuntimeError(f"{spec.tag} ABI version {have} != {spec.abi}")
+    return lib
+
+
+def _profile_symbols(tag):
+    """The four exports csrc/launch_prof.h's LPROF_EXPORTS(tag) emits, in the order the headers declare them."""
+    return {
+        tag + "_profile_enable": (C.c_int, [C.c_int]),
+        tag + "_profile_collect": (C.c_int, []),
+        tag + "_profile_entry": (C.c_int, [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+        tag + "_profile_reset": (C.c_int, []),
+    }
+
+
+def handle(tag):
+    """The loaded library of a tag, through its module-level loader (and that loader's cache)."""
+    return globals()[tag]()
+
+
+def last_error(tag) -> str:
+    return getattr(handle(tag), tag + "_last_error")().decode("utf-8", "replace")
+
+
+def profile_enable(tags, on: bool) -> None:
+    """Event pairs around every launch of the libraries `tags` (csrc/launch_prof.h: <tag>_profile_*), each from an empty table;
+    libgsr's slot-based twin is gsr_profile_enable."""
+    for tag in tags:
+        lib = handle(tag)
+        getattr(lib, tag + "_profile_enable")(1 if on else 0)
+        if on:
+            getattr(lib, tag + "_profile_reset")()
+
+
+def profile_read(tags) -> dict:
+    """{kernel name: (total_ms, launches)} of the launches of the libraries `tags` since profile_enable(tags, True)."""
+    out = {}
+    for tag in tags:
+        lib = handle(tag)
+        for i in range(getattr(lib, tag + "_profile_collect")()):
+            name, ms, k = C.c_char_p(), C.c_double(), C.c_int64()
+            if getattr(lib, tag + "_profile_entry")(i, C.byref(name), C.byref(ms), C.byref(k)) == 0:
+                out[name.value.decode()] = (ms.value, k.value)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# libgsr_hip.so : the splat rasterizer (include/gsr.h)
+# ------------------------------------------------------------------------------------------------
+GSR_LIB_PATH = _lib_path("gsr", "GSR_LIB")
 
 GSR_OK = 0
 GSR_ABI_VERSION = 11
@@ -160,42 +253,22 @@ def gsr_wait_stats():
     return ms.value, n.value
 
 
+LIBS["gsr"] = LibSpec("gsr", GSR_LIB_PATH, GSR_SYMBOLS, GSR_ABI_VERSION)
 _gsr = None
-
-
-def _torch_first():
-    """The libraries take raw device pointers of torch tensors and launch on torch's streams, so they have to share torch's HIP
-    runtime: torch is imported before the first library is mapped.  (Mapped first -- e.g. build() followed by smoke() in one
-    process -- they pull in /opt/rocm's libamdhip64 ahead of the copy torch ships, and the first runtime call that needs the
-    device fails with 'no ROCm-capable device is detected'.)"""
-    import torch  # noqa: F401
 
 
 def gsr():
     """The rasterizer library; raises (never falls back) when it is not built."""
     global _gsr
     if _gsr is None:
-        if not os.path.exists(GSR_LIB_PATH):
-            raise RuntimeError(
-                f"{GSR_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(hipcc --offload-arch=gfx950).  There is no CPU fallback."
-            )
-        _torch_first()
-        lib = C.CDLL(GSR_LIB_PATH)
-        for name, (res, args) in GSR_SYMBOLS.items():
-            fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
-            fn.restype = res
-            fn.argtypes = args
-        if lib.gsr_abi_version() != GSR_ABI_VERSION:
-            raise RuntimeError(f"gsr ABI version {lib.gsr_abi_version()} != {GSR_ABI_VERSION}")
-        _gsr = lib
+        _gsr = _load(LIBS["gsr"])
     return _gsr
 
 
 # ------------------------------------------------------------------------------------------------
 # libgab_hip.so : FLAME / face-frame / splat binding kernels (include/gab.h)
 # ------------------------------------------------------------------------------------------------
-GAB_LIB_PATH = os.environ.get("GAB_LIB") or os.path.join(_HERE, "libgab_hip.so")   # (GAB_LIB: experiment builds, as GSR_LIB)
+GAB_LIB_PATH = _lib_path("gab", "GAB_LIB")
 GAB_FLAME_WS_FLOATS = 512
 GAB_BIND_ROW_FLOATS = 20   # include/gab.h: floats per splat of the two-pass CSR backward's scratch
 _P = C.c_void_p
@@ -230,13 +303,11 @@ GAB_SYMBOLS = {
     "gab_bind_backward_faces": (C.c_int, [C.c_int32, _P, _P, _P, _P]),
     "gab_zero_buffers": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), _P]),
     "gab_feed_row": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P]),
-    "gab_profile_enable": (C.c_int, [C.c_int]),
-    "gab_profile_collect": (C.c_int, []),
-    "gab_profile_entry": (C.c_int, [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
-    "gab_profile_reset": (C.c_int, []),
+    **_profile_symbols("gab"),
 }
 GAB_ABI_VERSION = 5
 
+LIBS["gab"] = LibSpec("gab", GAB_LIB_PATH, GAB_SYMBOLS, GAB_ABI_VERSION)
 _gab = None
 
 
@@ -244,24 +315,14 @@ def gab():
     """The binding library; raises (never falls back) when it is not built."""
     global _gab
     if _gab is None:
-        if not os.path.exists(GAB_LIB_PATH):
-            raise RuntimeError(f"{GAB_LIB_PATH} is missing: run __graft_entry__.build() (hipcc, gfx950).  There is no CPU fallback.")
-        _torch_first()
-        lib = C.CDLL(GAB_LIB_PATH)
-        for name, (res, args) in GAB_SYMBOLS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.gab_abi_version() != GAB_ABI_VERSION:
-            raise RuntimeError(f"gab ABI version {lib.gab_abi_version()} != {GAB_ABI_VERSION}")
-        _gab = lib
+        _gab = _load(LIBS["gab"])
     return _gab
 
 
 # ------------------------------------------------------------------------------------------------
 # libgls_hip.so : fused L1 + SSIM loss and densification statistics (include/gls.h)
 # ------------------------------------------------------------------------------------------------
-GLS_LIB_PATH = os.path.join(_HERE, "libgls_hip.so")
+GLS_LIB_PATH = _lib_path("gls")
 GLS_SYMBOLS = {
     "gls_abi_version": (C.c_int, []),
     "gls_last_error": (C.c_char_p, []),
@@ -274,13 +335,11 @@ GLS_SYMBOLS = {
     "gls_l1_backward": (C.c_int, [C.c_int64, _P, _P, _P, C.c_float, _P, _P]),
     "gls_densification_stats": (C.c_int, [C.c_int32] + [_P] * 6),
     "gls_add_densification_stats": (C.c_int, [C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
-    "gls_profile_enable": (C.c_int, [C.c_int]),
-    "gls_profile_collect": (C.c_int, []),
-    "gls_profile_entry": (C.c_int, [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
-    "gls_profile_reset": (C.c_int, []),
+    **_profile_symbols("gls"),
 }
 GLS_ABI_VERSION = 4
 
+LIBS["gls"] = LibSpec("gls", GLS_LIB_PATH, GLS_SYMBOLS, GLS_ABI_VERSION)
 _gls = None
 
 
@@ -288,57 +347,23 @@ def gls():
     """The loss / statistics library; raises (never falls back) when it is not built."""
     global _gls
     if _gls is None:
-        if not os.path.exists(GLS_LIB_PATH):
-            raise RuntimeError(f"{GLS_LIB_PATH} is missing: run __graft_entry__.build() (hipcc, gfx950).  There is no CPU fallback.")
-        _torch_first()
-        lib = C.CDLL(GLS_LIB_PATH)
-        for name, (res, args) in GLS_SYMBOLS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.gls_abi_version() != GLS_ABI_VERSION:
-            raise RuntimeError(f"gls ABI version {lib.gls_abi_version()} != {GLS_ABI_VERSION}")
-        _gls = lib
+        _gls = _load(LIBS["gls"])
     return _gls
 
 
-def launch_profile_enable(on: bool) -> None:
-    """Event pairs around every launch of libgab / libgls (include/gab.h, gls.h: *_profile_*); libgsr's twin is gsr_profile_enable."""
-    for lib, tag in ((gab(), "gab"), (gls(), "gls")):
-        getattr(lib, tag + "_profile_enable")(1 if on else 0)
-        if on:
-            getattr(lib, tag + "_profile_reset")()
-
-
-def launch_profile_read() -> dict:
-    """{kernel name: (total_ms, launches)} of libgab's and libgls's launches since launch_profile_enable(True)."""
-    out = {}
-    for lib, tag in ((gab(), "gab"), (gls(), "gls")):
-        n = getattr(lib, tag + "_profile_collect")()
-        for i in range(n):
-            name, ms, k = C.c_char_p(), C.c_double(), C.c_int64()
-            if getattr(lib, tag + "_profile_entry")(i, C.byref(name), C.byref(ms), C.byref(k)) == 0:
-                out[name.value.decode()] = (ms.value, k.value)
-    return out
-
-
-def gls_error() -> str:
-    return gls().gls_last_error().decode("utf-8", "replace")
-
-
-def gab_error() -> str:
-    return gab().gab_last_error().decode("utf-8", "replace")
-
-
-def gsr_error() -> str:
-    return gsr().gsr_last_error().decode("utf-8", "replace")
+# libgab's and libgls's launches together: what bench.py's roofline.all_kernels is built from
+launch_profile_enable = partial(profile_enable, ("gab", "gls"))
+launch_profile_read = partial(profile_read, ("gab", "gls"))
+gsr_error = partial(last_error, "gsr")
+gab_error = partial(last_error, "gab")
+gls_error = partial(last_error, "gls")
 
 
 # ------------------------------------------------------------------------------------------------
 # libgmr_hip.so : the mesh overlay's triangle rasterizer and antialias (include/gmr.h).  Loaded only by mesh_raster.py:
 # the splat path never maps it.
 # ------------------------------------------------------------------------------------------------
-GMR_LIB_PATH = os.path.join(_HERE, "libgmr_hip.so")
+GMR_LIB_PATH = _lib_path("gmr")
 GMR_SYMBOLS = {
     "gmr_abi_version": (C.c_int, []),
     "gmr_last_error": (C.c_char_p, []),
@@ -349,6 +374,7 @@ GMR_SYMBOLS = {
 GMR_ABI_VERSION = 1
 GMR_MAX_TRIANGLES = (1 << 24) - 1   # include/gmr.h: triangle_id + 1 is stored as an exact float
 
+LIBS["gmr"] = LibSpec("gmr", GMR_LIB_PATH, GMR_SYMBOLS, GMR_ABI_VERSION)
 _gmr = None
 
 
@@ -356,28 +382,17 @@ def gmr():
     """The mesh rasterizer library; raises (never falls back) when it is not built."""
     global _gmr
     if _gmr is None:
-        if not os.path.exists(GMR_LIB_PATH):
-            raise RuntimeError(f"{GMR_LIB_PATH} is missing: run __graft_entry__.build() (hipcc, gfx950).  There is no CPU fallback.")
-        _torch_first()
-        lib = C.CDLL(GMR_LIB_PATH)
-        for name, (res, args) in GMR_SYMBOLS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.gmr_abi_version() != GMR_ABI_VERSION:
-            raise RuntimeError(f"gmr ABI version {lib.gmr_abi_version()} != {GMR_ABI_VERSION}")
-        _gmr = lib
+        _gmr = _load(LIBS["gmr"])
     return _gmr
 
 
-def gmr_error() -> str:
-    return gmr().gmr_last_error().decode("utf-8", "replace")
+gmr_error = partial(last_error, "gmr")
 
 
 # ------------------------------------------------------------------------------------------------
 # libgop_hip.so : the fused Adam step (include/gop.h).  Loaded only by optim.py, at the first step on device tensors.
 # ------------------------------------------------------------------------------------------------
-GOP_LIB_PATH = os.path.join(_HERE, "libgop_hip.so")
+GOP_LIB_PATH = _lib_path("gop")
 GOP_ABI_VERSION = 1
 GOP_MAX_TENSORS = 32   # include/gop.h: tensors per launch
 GOP_SLAB = 2048        # include/gop.h: elements per workgroup
@@ -394,12 +409,10 @@ GOP_SYMBOLS = {
     "gop_last_error": (C.c_char_p, []),
     "gop_adam_step": (C.c_int, [C.c_int32, C.POINTER(GopAdamTensor), C.c_float, C.c_float, C.c_float, _P]),
     "gop_adam_step_ex": (C.c_int, [C.c_int32, C.POINTER(GopAdamTensor)] + [C.c_float] * 5 + [_P]),
-    "gop_profile_enable": (C.c_int, [C.c_int]),
-    "gop_profile_collect": (C.c_int, []),
-    "gop_profile_entry": (C.c_int, [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
-    "gop_profile_reset": (C.c_int, []),
+    **_profile_symbols("gop"),
 }
 
+LIBS["gop"] = LibSpec("gop", GOP_LIB_PATH, GOP_SYMBOLS, GOP_ABI_VERSION)
 _gop = None
 
 
@@ -407,45 +420,19 @@ def gop():
     """The optimizer library; raises (never falls back) when it is not built."""
     global _gop
     if _gop is None:
-        if not os.path.exists(GOP_LIB_PATH):
-            raise RuntimeError(f"{GOP_LIB_PATH} is missing: run __graft_entry__.build() (hipcc, gfx950).  There is no CPU fallback.")
-        _torch_first()
-        lib = C.CDLL(GOP_LIB_PATH)
-        for name, (res, args) in GOP_SYMBOLS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.gop_abi_version() != GOP_ABI_VERSION:
-            raise RuntimeError(f"gop ABI version {lib.gop_abi_version()} != {GOP_ABI_VERSION}")
-        _gop = lib
+        _gop = _load(LIBS["gop"])
     return _gop
 
 
-def gop_error() -> str:
-    return gop().gop_last_error().decode("utf-8", "replace")
-
-
-def gop_profile_enable(on: bool) -> None:
-    """Event pairs around every launch of libgop (include/gop.h: gop_profile_*), from an empty table."""
-    gop().gop_profile_enable(1 if on else 0)
-    if on:
-        gop().gop_profile_reset()
-
-
-def gop_profile_read() -> dict:
-    """{kernel name: (total_ms, launches)} of libgop's launches since gop_profile_enable(True)."""
-    out = {}
-    for i in range(gop().gop_profile_collect()):
-        name, ms, k = C.c_char_p(), C.c_double(), C.c_int64()
-        if gop().gop_profile_entry(i, C.byref(name), C.byref(ms), C.byref(k)) == 0:
-            out[name.value.decode()] = (ms.value, k.value)
-    return out
+gop_error = partial(last_error, "gop")
+gop_profile_enable = partial(profile_enable, ("gop",))
+gop_profile_read = partial(profile_read, ("gop",))
 
 
 # ------------------------------------------------------------------------------------------------
 # libgrl_hip.so : the fused splat regularisers (include/grl.h).  Loaded only by loss.splat_regularizers, at the first call on device tensors.
 # ------------------------------------------------------------------------------------------------
-GRL_LIB_PATH = os.path.join(_HERE, "libgrl_hip.so")
+GRL_LIB_PATH = _lib_path("grl")
 GRL_ABI_VERSION = 1
 GRL_SLAB = 1024               # include/grl.h: splats per workgroup
 GRL_MAX_SPLATS = 1 << 24      # include/grl.h: P must stay below this (the count is an exact float)
@@ -456,12 +443,10 @@ GRL_SYMBOLS = {
     "grl_scratch_bytes": (C.c_int64, [C.c_int32]),
     "grl_forward": (C.c_int, [C.c_int32, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P]),
     "grl_backward": (C.c_int, [C.c_int32, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P]),
-    "grl_profile_enable": (C.c_int, [C.c_int]),
-    "grl_profile_collect": (C.c_int, []),
-    "grl_profile_entry": (C.c_int, [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
-    "grl_profile_reset": (C.c_int, []),
+    **_profile_symbols("grl"),
 }
 
+LIBS["grl"] = LibSpec("grl", GRL_LIB_PATH, GRL_SYMBOLS, GRL_ABI_VERSION)
 _grl = None
 
 
@@ -469,36 +454,10 @@ def grl():
     """The regulariser library; raises (never falls back) when it is not built."""
     global _grl
     if _grl is None:
-        if not os.path.exists(GRL_LIB_PATH):
-            raise RuntimeError(f"{GRL_LIB_PATH} is missing: run __graft_entry__.build() (hipcc, gfx950).  There is no CPU fallback.")
-        _torch_first()
-        lib = C.CDLL(GRL_LIB_PATH)
-        for name, (res, args) in GRL_SYMBOLS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.grl_abi_version() != GRL_ABI_VERSION:
-            raise RuntimeError(f"grl ABI version {lib.grl_abi_version()} != {GRL_ABI_VERSION}")
-        _grl = lib
+        _grl = _load(LIBS["grl"])
     return _grl
 
 
-def grl_error() -> str:
-    return grl().grl_last_error().decode("utf-8", "replace")
-
-
-def grl_profile_enable(on: bool) -> None:
-    """Event pairs around every launch of libgrl (include/grl.h: grl_profile_*), from an empty table."""
-    grl().grl_profile_enable(1 if on else 0)
-    if on:
-        grl().grl_profile_reset()
-
-
-def grl_profile_read() -> dict:
-    """{kernel name: (total_ms, launches)} of libgrl's launches since grl_profile_enable(True)."""
-    out = {}
-    for i in range(grl().grl_profile_collect()):
-        name, ms, k = C.c_char_p(), C.c_double(), C.c_int64()
-        if grl().grl_profile_entry(i, C.byref(name), C.byref(ms), C.byref(k)) == 0:
-            out[name.value.decode()] = (ms.value, k.value)
-    return out
+grl_error = partial(last_error, "grl")
+grl_profile_enable = partial(profile_enable, ("grl",))
+grl_profile_read = partial(profile_read, ("grl",))

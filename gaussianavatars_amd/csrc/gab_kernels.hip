@@ -13,11 +13,9 @@
 #include <hip/hip_runtime.h>
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
-#include <cstdarg>
-#include <cstdio>
-
 #include "../../include/gab.h"
 #include "launch_prof.h"
+#include "lib_common.h"
 #include "bind_math.h"
 
 namespace gab {
@@ -1560,24 +1558,10 @@ __global__ __launch_bounds__(256) void k_zero_many(ZeroSpec z)
 // C ABI
 // =================================================================================================
 namespace {
-thread_local char g_err[512] = "";
-int fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
 #define HIP_TRY(expr)                                                                                    \
     do {                                                                                                 \
         hipError_t e_ = (expr);                                                                          \
         if (e_ != hipSuccess) return fail(GAB_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));     \
-    } while (0)
-#define LAUNCH_CHECK(name)                                                                               \
-    do {                                                                                                 \
-        hipError_t e_ = hipGetLastError();                                                               \
-        if (e_ != hipSuccess) return fail(GAB_E_HIP, "launch of %s failed: %s", name, hipGetErrorString(e_)); \
     } while (0)
 
 int to_rig(const GabRig* r, gab::Rig* o)
@@ -1612,15 +1596,15 @@ int gab_flame_forward(const GabRig* rig_, const float* shape, const float* expr,
     hipStream_t st = (hipStream_t)stream_;
     const int E = 3 * rig.V;
     PROF_LAUNCH(gab::k_blend, dim3((E + 3) / 4), dim3(256), 0, st, rig, shape, expr, static_offset, v_shaped);
-    LAUNCH_CHECK("k_blend");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_blend failed");
     const bool flame_tree = rig.parents[1] == 0 && rig.parents[2] == 1 && rig.parents[3] == 1 && rig.parents[4] == 1;
     if (flame_tree)
         PROF_LAUNCH(gab::k_joints_chain<true>, dim3(1), dim3(1024), 0, st, rig, (const float*)v_shaped, rotation, neck, jaw, eyes, ws);
     else
         PROF_LAUNCH(gab::k_joints_chain<false>, dim3(1), dim3(1024), 0, st, rig, (const float*)v_shaped, rotation, neck, jaw, eyes, ws);
-    LAUNCH_CHECK("k_joints_chain");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_joints_chain failed");
     PROF_LAUNCH(gab::k_skin, dim3((rig.V + 255) / 256), dim3(256), 0, st, rig, (const float*)ws, (const float*)v_shaped, translation, verts);
-    LAUNCH_CHECK("k_skin");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_skin failed");
     return GAB_OK;
 }
 
@@ -1649,16 +1633,16 @@ int gab_flame_backward(const GabRig* rig_, const float* shape, const float* expr
     hipStream_t st = (hipStream_t)stream_;
     const int E = 3 * rig.V;
     PROF_LAUNCH(gab::k_skin_bwd, dim3((rig.V + 255) / 256), dim3(256), 0, st, rig, ws, v_shaped, dL_dverts, scratch, zs);
-    LAUNCH_CHECK("k_skin_bwd");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_skin_bwd failed");
     const bool flame_tree = rig.parents[1] == 0 && rig.parents[2] == 1 && rig.parents[3] == 1 && rig.parents[4] == 1;
     if (flame_tree)
         PROF_LAUNCH(gab::k_chain_bwd<true>, dim3(1), dim3(64), 0, st, rig, ws, rotation, neck, jaw, eyes, d_rotation, d_neck, d_jaw, d_eyes, d_translation, d_expr, d_shape);
     else
         PROF_LAUNCH(gab::k_chain_bwd<false>, dim3(1), dim3(64), 0, st, rig, ws, rotation, neck, jaw, eyes, d_rotation, d_neck, d_jaw, d_eyes, d_translation, d_expr, d_shape);
-    LAUNCH_CHECK("k_chain_bwd");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_chain_bwd failed");
     PROF_LAUNCH(gab::k_blend_bwd, dim3((E + GAB_BLEND_BWD_ROWS - 1) / GAB_BLEND_BWD_ROWS), dim3(256), 0, st, rig, (const float*)ws,
                        (const float*)scratch, dL_dv_shaped, d_static_offset, d_shape, d_expr);
-    LAUNCH_CHECK("k_blend_bwd");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_blend_bwd failed");
     return GAB_OK;
 }
 
@@ -1676,9 +1660,9 @@ int gab_flame_prepare(const GabRig* rig_, const float* shape, const float* stati
     hipStream_t st = (hipStream_t)stream_;
     const int E = 3 * rig.V, outs = 15 + 15 * rig.n_expr;
     PROF_LAUNCH(gab::k_prep_rows, dim3((E + 3) / 4), dim3(256), 0, st, rig, shape, static_offset, prepared);
-    LAUNCH_CHECK("k_prep_rows");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_prep_rows failed");
     PROF_LAUNCH(gab::k_prep_joints, dim3((outs + 3) / 4), dim3(256), 0, st, rig, prepared);
-    LAUNCH_CHECK("k_prep_joints");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_prep_joints failed");
     return GAB_OK;
 }
 
@@ -1697,7 +1681,7 @@ int gab_flame_forward_prepared(const GabRig* rig_, const float* prepared, const 
         PROF_LAUNCH(gab::k_flame_fused<true>, dim3(blocks), dim3(256), 0, st, rig, prepared, expr, rotation, neck, jaw, eyes, translation, verts, v_shaped, ws, (const float*)nullptr);
     else
         PROF_LAUNCH(gab::k_flame_fused<false>, dim3(blocks), dim3(256), 0, st, rig, prepared, expr, rotation, neck, jaw, eyes, translation, verts, v_shaped, ws, (const float*)nullptr);
-    LAUNCH_CHECK("k_flame_fused");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_flame_fused failed");
     return GAB_OK;
 }
 
@@ -1715,7 +1699,7 @@ int gab_blend_sequence(const GabRig* rig_, const float* prepared, const float* e
     const int MT = std::min(16, std::max(1, (mtiles * gx + 511) / 512));
     dim3 grid((unsigned)gx, (unsigned)((mtiles + MT - 1) / MT));
     PROF_LAUNCH(gab::k_blend_seq_mfma, grid, dim3(256), 0, (hipStream_t)stream_, rig, prepared, expr_table, (int)T, MT, v_shaped_seq);
-    LAUNCH_CHECK("k_blend_seq_mfma");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_blend_seq_mfma failed");
     return GAB_OK;
 }
 
@@ -1734,7 +1718,7 @@ int gab_flame_forward_sequence(const GabRig* rig_, const float* prepared, const 
         PROF_LAUNCH(gab::k_flame_fused<true>, dim3(blocks), dim3(256), 0, st, rig, prepared, expr, rotation, neck, jaw, eyes, translation, verts, v_shaped, ws, v_shaped_row);
     else
         PROF_LAUNCH(gab::k_flame_fused<false>, dim3(blocks), dim3(256), 0, st, rig, prepared, expr, rotation, neck, jaw, eyes, translation, verts, v_shaped, ws, v_shaped_row);
-    LAUNCH_CHECK("k_flame_fused");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_flame_fused failed");
     return GAB_OK;
 }
 
@@ -1763,7 +1747,7 @@ int gab_flame_backward_prepared(const GabRig* rig_, const float* prepared, const
     hipStream_t st = (hipStream_t)stream_;
     const int E = 3 * rig.V;
     PROF_LAUNCH(gab::k_skin_bwd, dim3((rig.V + 255) / 256), dim3(256), 0, st, rig, ws, v_shaped, dL_dverts, scratch, zs);
-    LAUNCH_CHECK("k_skin_bwd");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_skin_bwd failed");
     const float* Mmat = prepared + gab::prep_joint_offset(rig.V) + 16;
     const int blocks = 1 + (E + GAB_BLEND_BWD_ROWS - 1) / GAB_BLEND_BWD_ROWS;
     const bool flame_tree = rig.parents[1] == 0 && rig.parents[2] == 1 && rig.parents[3] == 1 && rig.parents[4] == 1;
@@ -1773,7 +1757,7 @@ int gab_flame_backward_prepared(const GabRig* rig_, const float* prepared, const
     else
         PROF_LAUNCH(gab::k_chain_blend_bwd<false>, dim3(blocks), dim3(256), 0, st, rig, ws, (const float*)scratch, Mmat, rotation, neck, jaw, eyes,
                            d_rotation, d_neck, d_jaw, d_eyes, d_translation, d_expr);
-    LAUNCH_CHECK("k_chain_blend_bwd");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_chain_blend_bwd failed");
     return GAB_OK;
 }
 
@@ -1808,7 +1792,7 @@ int gab_mesh_backward_prepared(const GabRig* rig_, const float* prepared, const 
     a.g_vs = scratch;
     hipStream_t st = (hipStream_t)stream_;
     PROF_LAUNCH(gab::k_gather_skin_bwd, dim3((rig.V + GAB_MESH_VPB - 1) / GAB_MESH_VPB), dim3(256), 0, st, rig, a, zs);
-    LAUNCH_CHECK("k_gather_skin_bwd");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_gather_skin_bwd failed");
     const int E = 3 * rig.V;
     const float* Mmat = prepared + gab::prep_joint_offset(rig.V) + 16;
     const int blocks = 1 + (E + GAB_BLEND_BWD_ROWS - 1) / GAB_BLEND_BWD_ROWS;
@@ -1819,7 +1803,7 @@ int gab_mesh_backward_prepared(const GabRig* rig_, const float* prepared, const 
     else
         PROF_LAUNCH(gab::k_chain_blend_bwd<false>, dim3(blocks), dim3(256), 0, st, rig, ws, (const float*)scratch, Mmat, rotation, neck, jaw, eyes,
                            d_rotation, d_neck, d_jaw, d_eyes, d_translation, d_expr);
-    LAUNCH_CHECK("k_chain_blend_bwd");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_chain_blend_bwd failed");
     return GAB_OK;
 }
 
@@ -1834,7 +1818,7 @@ int gab_face_frames_forward(int32_t V, int32_t F, const float* verts, const void
     if (!verts || !faces || !center || !orien_mat || !scaling || !orien_quat) return fail(GAB_E_ARG, "gab_face_frames_forward: NULL buffer");
     PROF_LAUNCH(gab::k_face_frames, dim3((F + 255) / 256), dim3(256), 0, (hipStream_t)stream_, F, verts, faces, is64, center, orien_mat,
                        scaling, orien_quat, d_verts_zeroed, 3 * V);
-    LAUNCH_CHECK("k_face_frames");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_face_frames failed");
     return GAB_OK;
 }
 
@@ -1850,7 +1834,7 @@ int gab_face_frames_backward(int32_t V, int32_t F, const float* verts, const voi
     if (!verts || !faces) return fail(GAB_E_ARG, "gab_face_frames_backward: NULL buffer");
     PROF_LAUNCH(gab::k_face_frames_bwd, dim3((F + 255) / 256), dim3(256), 0, st, F, verts, faces, is64, d_center, d_orien_mat, d_scaling,
                        d_orien_quat, d_verts);
-    LAUNCH_CHECK("k_face_frames_bwd");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_face_frames_bwd failed");
     return GAB_OK;
 }
 
@@ -1867,7 +1851,7 @@ int gab_bind_forward(int32_t N, int32_t F, const float* xyz, const float* log_sc
         return fail(GAB_E_ARG, "gab_bind_forward: NULL buffer");
     PROF_LAUNCH(gab::k_bind, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream_, N, xyz, log_scaling, rotation, binding, is64,
                        face_center, face_orien_mat, face_scaling, face_orien_quat, out_xyz, out_scaling, out_rotation, opacity_logit, out_opacity);
-    LAUNCH_CHECK("k_bind");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_bind failed");
     return GAB_OK;
 }
 
@@ -1890,7 +1874,7 @@ int gab_bind_backward(int32_t N, int32_t F, const float* xyz, const float* log_s
     PROF_LAUNCH(gab::k_bind_bwd, dim3((N + 255) / 256), dim3(256), 0, st, N, xyz, log_scaling, rotation, binding, is64, face_orien_mat,
                        face_scaling, face_orien_quat, d_out_xyz, d_out_scaling, d_out_rotation, d_xyz, d_log_scaling, d_rotation, d_face, F,
                        out_opacity, d_out_opacity, d_opacity_logit);
-    LAUNCH_CHECK("k_bind_bwd");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_bind_bwd failed");
     return GAB_OK;
 }
 
@@ -1913,17 +1897,17 @@ int gab_bind_backward_csr(int32_t N, int32_t F, const float* xyz, const float* l
             PROF_LAUNCH(gab::k_bind_bwd_rows, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, N, xyz, log_scaling,
                                rotation, splat_face, slot, face_orien_mat, face_scaling, face_orien_quat, d_out_xyz, d_out_scaling,
                                d_out_rotation, d_xyz, d_log_scaling, d_rotation, rows, out_opacity, d_out_opacity, d_opacity_logit);
-            LAUNCH_CHECK("k_bind_bwd_rows");
+            LAUNCH_CHECK(GAB_E_HIP, "launch of k_bind_bwd_rows failed");
         }
         PROF_LAUNCH(gab::k_bind_bwd_faces, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, F, face_begin,
                            (const float*)rows, d_face);
-        LAUNCH_CHECK("k_bind_bwd_faces");
+        LAUNCH_CHECK(GAB_E_HIP, "launch of k_bind_bwd_faces failed");
         return GAB_OK;
     }
     PROF_LAUNCH(gab::k_bind_bwd_csr, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, F, xyz, log_scaling,
                        rotation, face_orien_mat, face_scaling, face_orien_quat, d_out_xyz, d_out_scaling, d_out_rotation, order, face_begin,
                        d_xyz, d_log_scaling, d_rotation, d_face, out_opacity, d_out_opacity, d_opacity_logit);
-    LAUNCH_CHECK("k_bind_bwd_csr");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_bind_bwd_csr failed");
     return GAB_OK;
 }
 
@@ -1932,7 +1916,7 @@ int gab_bind_backward_faces(int32_t F, const int32_t* face_begin, const float* r
     if (F <= 0 || !face_begin || !rows || !d_face) return fail(GAB_E_ARG, "gab_bind_backward_faces: bad arguments");
     const long long threads = 16ll * F;
     PROF_LAUNCH(gab::k_bind_bwd_faces, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, F, face_begin, rows, d_face);
-    LAUNCH_CHECK("k_bind_bwd_faces");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_bind_bwd_faces failed");
     return GAB_OK;
 }
 
@@ -1941,7 +1925,7 @@ int gab_feed_row(const float* packed, int32_t T, int32_t width, const int32_t* s
 {
     if (T <= 0 || width <= 0 || !packed || !cursor || !row || (schedule && n_sched <= 0)) return fail(GAB_E_ARG, "gab_feed_row: bad arguments");
     PROF_LAUNCH(gab::k_feed_row, dim3(1), dim3(256), 0, (hipStream_t)stream_, packed, T, width, schedule, n_sched, cursor, row);
-    LAUNCH_CHECK("k_feed_row");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_feed_row failed");
     return GAB_OK;
 }
 
@@ -1962,27 +1946,10 @@ int gab_zero_buffers(int32_t count, float* const* buffers_host, const int32_t* s
     if (bx < 1) bx = 1;
     if (bx > 64) bx = 64;
     PROF_LAUNCH(gab::k_zero_many, dim3(bx, count), dim3(256), 0, (hipStream_t)stream_, z);
-    LAUNCH_CHECK("k_zero_many");
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_zero_many failed");
     return GAB_OK;
 }
 
-int gab_profile_enable(int on)
-{
-    lprof::g.on.store(on ? 1 : 0);
-    return 0;
-}
-int gab_profile_collect(void) { return lprof::collect(); }
-int gab_profile_entry(int32_t index, const char** name, double* total_ms, int64_t* launches)
-{
-    long long n = 0;
-    const int rc = lprof::entry(index, name, total_ms, &n);
-    if (launches) *launches = (int64_t)n;
-    return rc;
-}
-int gab_profile_reset(void)
-{
-    lprof::reset();
-    return 0;
-}
+LPROF_EXPORTS(gab)
 
 }  // extern "C"

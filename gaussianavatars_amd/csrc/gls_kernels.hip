@@ -10,12 +10,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 
 #include "../../include/gls.h"
 #include "launch_prof.h"
+#include "lib_common.h"
 
 namespace gls {
 
@@ -339,21 +338,6 @@ __global__ __launch_bounds__(256) void k_add_densify_stats(int P, const unsigned
 }  // namespace gls
 
 // ---------------------------------------------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-static int fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-#define LAUNCH_CHECK(what)                                                                            \
-    do {                                                                                              \
-        hipError_t e_ = hipGetLastError();                                                            \
-        if (e_ != hipSuccess) return fail(GLS_E_HIP, "%s: %s", what, hipGetErrorString(e_));          \
-    } while (0)
-
 static gls::Window make_window()
 {
     // utils/loss_utils.py:23-25: exp(-(x - 5)^2 / (2 * 1.5^2)) held in fp32, divided by its fp32 sum
@@ -394,9 +378,9 @@ int gls_l1_ssim_forward(int32_t B, int32_t C, int32_t H, int32_t W, const float*
     const dim3 grid((W + gls::TX - 1) / gls::TX, (H + gls::TY - 1) / gls::TY, B * C);
     const size_t stride = (size_t)B * C * H * W;
     PROF_LAUNCH(gls::k_l1_ssim_fwd, grid, dim3(256), 0, stream, H, W, img1, img2, make_window(), maps, stride, (float2*)partial);
-    LAUNCH_CHECK("k_l1_ssim_fwd");
+    LAUNCH_CHECK(GLS_E_HIP, "k_l1_ssim_fwd");
     PROF_LAUNCH(gls::k_reduce_partials, dim3(B), dim3(256), 0, stream, (const float2*)partial, (int)(grid.x * grid.y * C), scale, (float2*)sums);
-    LAUNCH_CHECK("k_reduce_partials");
+    LAUNCH_CHECK(GLS_E_HIP, "k_reduce_partials");
     return GLS_OK;
 }
 
@@ -409,7 +393,7 @@ static int l1_ssim_backward_impl(int32_t B, int32_t C, int32_t H, int32_t W, con
     const dim3 grid((W + gls::TX - 1) / gls::TX, (H + gls::TY - 1) / gls::TY, B * C);
     const size_t stride = (size_t)B * C * H * W;
     PROF_LAUNCH(gls::k_l1_ssim_bwd, grid, dim3(256), 0, stream, C, H, W, img1, img2, maps, stride, make_window(), g_l1, g_ssim, g_stride, scale, d_img1);
-    LAUNCH_CHECK("k_l1_ssim_bwd");
+    LAUNCH_CHECK(GLS_E_HIP, "k_l1_ssim_bwd");
     return GLS_OK;
 }
 
@@ -479,14 +463,14 @@ static int l1_forward_impl(int64_t n, const float* a, const float* b, float scal
         const int fb = wide < 1 ? 1 : (wide > fmax ? fmax : wide);
         if (grad) PROF_LAUNCH(gls::k_l1_fwd_1g, dim3(fb), dim3(fthreads), 0, stream, (long long)n, a, b, (float2*)partial, scale, d_a, word, sum);
         else PROF_LAUNCH(gls::k_l1_fwd_1, dim3(fb), dim3(fthreads), 0, stream, (long long)n, a, b, (float2*)partial, scale, (float*)nullptr, word, sum);
-        LAUNCH_CHECK("k_l1_fwd");
+        LAUNCH_CHECK(GLS_E_HIP, "k_l1_fwd");
         return GLS_OK;
     }
     if (grad) PROF_LAUNCH(gls::k_l1_fwd_2g, dim3(blocks), dim3(256), 0, stream, (long long)n, a, b, (float2*)partial, scale, d_a, (unsigned long long*)nullptr, (float*)nullptr);
     else PROF_LAUNCH(gls::k_l1_fwd_2, dim3(blocks), dim3(256), 0, stream, (long long)n, a, b, (float2*)partial, scale, (float*)nullptr, (unsigned long long*)nullptr, (float*)nullptr);
-    LAUNCH_CHECK("k_l1_fwd");
+    LAUNCH_CHECK(GLS_E_HIP, "k_l1_fwd");
     PROF_LAUNCH(gls::k_l1_reduce, dim3(1), dim3(256), 0, stream, (const float2*)partial, blocks, scale, sum);
-    LAUNCH_CHECK("k_l1_reduce");
+    LAUNCH_CHECK(GLS_E_HIP, "k_l1_reduce");
     return GLS_OK;
 }
 
@@ -509,7 +493,7 @@ int gls_l1_backward(int64_t n, const float* a, const float* b, const float* g, f
     int blocks = (int)(((n >> 2) + 255) / 256);
     blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);
     PROF_LAUNCH(gls::k_l1_bwd, dim3(blocks), dim3(256), 0, stream, (long long)n, a, b, g, scale, d_a);
-    LAUNCH_CHECK("k_l1_bwd");
+    LAUNCH_CHECK(GLS_E_HIP, "k_l1_bwd");
     return GLS_OK;
 }
 
@@ -521,7 +505,7 @@ int gls_densification_stats(int32_t P, const int32_t* radii, const float* viewsp
     if (!radii || !viewspace_grad || !max_radii2D || !xyz_gradient_accum || !denom) return fail(GLS_E_ARG, "null pointer");
     PROF_LAUNCH(gls::k_densify_stats, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream_, P, radii, viewspace_grad,
                        max_radii2D, xyz_gradient_accum, denom);
-    LAUNCH_CHECK("k_densify_stats");
+    LAUNCH_CHECK(GLS_E_HIP, "k_densify_stats");
     return GLS_OK;
 }
 
@@ -533,27 +517,10 @@ int gls_add_densification_stats(int32_t P, const uint8_t* update_filter, const f
     if (!update_filter || !viewspace_grad || !xyz_gradient_accum || !denom) return fail(GLS_E_ARG, "null pointer");
     PROF_LAUNCH(gls::k_add_densify_stats, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream_, P, update_filter, viewspace_grad, grad_stride,
                        xyz_gradient_accum, denom);
-    LAUNCH_CHECK("k_add_densify_stats");
+    LAUNCH_CHECK(GLS_E_HIP, "k_add_densify_stats");
     return GLS_OK;
 }
 
-int gls_profile_enable(int on)
-{
-    lprof::g.on.store(on ? 1 : 0);
-    return 0;
-}
-int gls_profile_collect(void) { return lprof::collect(); }
-int gls_profile_entry(int32_t index, const char** name, double* total_ms, int64_t* launches)
-{
-    long long n = 0;
-    const int rc = lprof::entry(index, name, total_ms, &n);
-    if (launches) *launches = (int64_t)n;
-    return rc;
-}
-int gls_profile_reset(void)
-{
-    lprof::reset();
-    return 0;
-}
+LPROF_EXPORTS(gls)
 
 }  // extern "C"

@@ -17,10 +17,9 @@
 
 #include <climits>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 
 #include "../../include/gmr.h"
+#include "lib_common.h"
 
 namespace gmr {
 
@@ -376,21 +375,6 @@ __global__ __launch_bounds__(NT) void k_mesh_antialias(int32_t B, int32_t V, int
 }  // namespace gmr
 
 // ---------------------------------------------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-static int fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-#define LAUNCH_CHECK(what)                                                                            \
-    do {                                                                                              \
-        hipError_t e_ = hipGetLastError();                                                            \
-        if (e_ != hipSuccess) return fail(GMR_E_HIP, "%s: %s", what, hipGetErrorString(e_));          \
-    } while (0)
-
 static bool shape_ok(int32_t B, int32_t V, int32_t F, int32_t H, int32_t W)
 {
     return B >= 1 && B <= 65535 && V >= 0 && F >= 0 && F <= GMR_MAX_TRIANGLES && H >= 1 && W >= 1 &&
@@ -423,11 +407,11 @@ int gmr_rasterize(int32_t B, int32_t V, int32_t F, int32_t H, int32_t W, const f
     int4* cbox = bbox + BF;
     if (F > 0) {
         hipLaunchKernelGGL(gmr::k_mesh_setup, dim3((unsigned)n_chunks(F), B), dim3(gmr::NT), 0, s, V, F, H, W, pos, tri, rec, bbox, cbox);
-        LAUNCH_CHECK("k_mesh_setup");
+        LAUNCH_CHECK(GMR_E_HIP, "k_mesh_setup");
     }
     dim3 grid((W + gmr::TS - 1) / gmr::TS, (H + gmr::TS - 1) / gmr::TS, B);
     hipLaunchKernelGGL(gmr::k_mesh_raster, grid, dim3(gmr::NT), 0, s, V, F, H, W, pos, tri, rec, bbox, cbox, (float4*)rast);
-    LAUNCH_CHECK("k_mesh_raster");
+    LAUNCH_CHECK(GMR_E_HIP, "k_mesh_raster");
     return GMR_OK;
 }
 
@@ -442,7 +426,7 @@ int gmr_antialias(int32_t B, int32_t V, int32_t F, int32_t H, int32_t W, int32_t
     const int64_t n = (int64_t)B * H * W;
     hipLaunchKernelGGL(gmr::k_mesh_antialias, dim3((unsigned)((n + gmr::NT - 1) / gmr::NT)), dim3(gmr::NT), 0, (hipStream_t)stream, B, V,
                        F, H, W, C, color, (const float4*)rast, pos, tri, neighbours, out);
-    LAUNCH_CHECK("k_mesh_antialias");
+    LAUNCH_CHECK(GMR_E_HIP, "k_mesh_antialias");
     return GMR_OK;
 }
 

@@ -13,12 +13,11 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 
 #include "../../include/gop.h"
 #include "launch_prof.h"
+#include "lib_common.h"
 
 namespace gop {
 
@@ -124,16 +123,6 @@ __global__ __launch_bounds__(BLOCK) void k_adam(const Table t, const Coef c)
 }  // namespace gop
 
 // ---------------------------------------------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-static int fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 extern "C" {
 
 int gop_abi_version(void) { return GOP_ABI_VERSION; }
@@ -180,8 +169,7 @@ int gop_adam_step_ex(int32_t ntensors, const GopAdamTensor* tensors, float beta1
             t.n[j] = 0, t.step_size[j] = 0.f, t.bc2_sqrt[j] = 1.f, t.unit_end[j] = INT_MAX;
         }
         PROF_LAUNCH(gop::k_adam, dim3((unsigned)units), dim3(gop::BLOCK), 0, stream, t, coef);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(GOP_E_HIP, "k_adam: %s", hipGetErrorString(e));
+        LAUNCH_CHECK(GOP_E_HIP, "k_adam");
     }
     return GOP_OK;
 }
@@ -191,23 +179,6 @@ int gop_adam_step(int32_t ntensors, const GopAdamTensor* tensors, float beta1, f
     return gop_adam_step_ex(ntensors, tensors, beta1, (float)(1.0 - (double)beta1), beta2, (float)(1.0 - (double)beta2), eps, stream);
 }
 
-int gop_profile_enable(int on)
-{
-    lprof::g.on.store(on ? 1 : 0);
-    return 0;
-}
-int gop_profile_collect(void) { return lprof::collect(); }
-int gop_profile_entry(int32_t index, const char** name, double* total_ms, int64_t* launches)
-{
-    long long n = 0;
-    const int rc = lprof::entry(index, name, total_ms, &n);
-    if (launches) *launches = (int64_t)n;
-    return rc;
-}
-int gop_profile_reset(void)
-{
-    lprof::reset();
-    return 0;
-}
+LPROF_EXPORTS(gop)
 
 }  // extern "C"

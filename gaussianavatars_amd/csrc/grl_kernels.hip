@@ -20,12 +20,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 
 #include "../../include/grl.h"
 #include "launch_prof.h"
+#include "lib_common.h"
 
 namespace grl {
 
@@ -248,16 +247,6 @@ __global__ __launch_bounds__(BLOCK) void k_reg_bwd(int P, const float* __restric
 }  // namespace grl
 
 // ---------------------------------------------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-static int fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 static inline bool aligned_to(const void* p, uintptr_t a) { return (((uintptr_t)p) & (a - 1)) == 0; }
 static inline int64_t workgroups(int32_t P) { return P > 0 ? ((int64_t)P + grl::SLAB - 1) / grl::SLAB : 1; }
 
@@ -300,8 +289,7 @@ int grl_forward(int32_t P, const void* xyz, const void* log_scaling, const void*
     else
         PROF_LAUNCH(grl::k_reg_fwd<false>, grid, block, 0, stream, (int)P, (const float*)xyz, (const float*)log_scaling, (const unsigned char*)visible,
                     threshold_xyz, threshold_scale, (float*)out, arrival, partials);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GRL_E_HIP, "k_reg_fwd: %s", hipGetErrorString(e));
+    LAUNCH_CHECK(GRL_E_HIP, "k_reg_fwd");
     return GRL_OK;
 }
 
@@ -327,28 +315,10 @@ int grl_backward(int32_t P, const void* xyz, const void* log_scaling, const void
     else
         PROF_LAUNCH(grl::k_reg_bwd<false>, grid, block, 0, stream, (int)P, (const float*)xyz, (const float*)log_scaling, (const unsigned char*)visible,
                     threshold_xyz, threshold_scale, (const float*)out, (const float*)g_xyz, (const float*)g_scale, (float*)d_xyz, (float*)d_log_scaling);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GRL_E_HIP, "k_reg_bwd: %s", hipGetErrorString(e));
+    LAUNCH_CHECK(GRL_E_HIP, "k_reg_bwd");
     return GRL_OK;
 }
 
-int grl_profile_enable(int on)
-{
-    lprof::g.on.store(on ? 1 : 0);
-    return 0;
-}
-int grl_profile_collect(void) { return lprof::collect(); }
-int grl_profile_entry(int32_t index, const char** name, double* total_ms, int64_t* launches)
-{
-    long long n = 0;
-    const int rc = lprof::entry(index, name, total_ms, &n);
-    if (launches) *launches = (int64_t)n;
-    return rc;
-}
-int grl_profile_reset(void)
-{
-    lprof::reset();
-    return 0;
-}
+LPROF_EXPORTS(grl)
 
 }  // extern "C"

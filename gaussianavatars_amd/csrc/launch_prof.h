@@ -1,4 +1,4 @@
-// launch_prof.h -- optional per-kernel timing of a library's launches with hipEvents on the launch stream (libgab / libgls; libgsr has its
+// launch_prof.h -- optional per-kernel timing of a library's launches with hipEvents on the launch stream (libgab / libgls / libgop / libgrl; libgsr has its
 // own slot-based twin in gsr_api.hip).  Off by default: a launch then costs one relaxed atomic load.  When on, every launch made through
 // PROF_LAUNCH is bracketed by an event pair; <lib>_profile_collect() synchronises the pending pairs and adds their elapsed times to a
 // small table keyed by the kernel's name (the text of the launch expression), which bench.py reads for roofline.all_kernels / roofline.step.
@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cstdint>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -91,3 +92,24 @@ static inline void reset()
         lprof::Scope prof_scope_(#kernel, (hipStream_t)(stream));                     \
         hipLaunchKernelGGL(kernel, grid, block, shmem, (hipStream_t)(stream), __VA_ARGS__); \
     } while (0)
+
+// the four entries include/<lib>.h declares over the table above: LPROF_EXPORTS(gab) defines gab_profile_enable / _collect / _entry / _reset
+#define LPROF_EXPORTS(lib)                                                                                        \
+    extern "C" int lib##_profile_enable(int on)                                                                   \
+    {                                                                                                             \
+        lprof::g.on.store(on ? 1 : 0);                                                                            \
+        return 0;                                                                                                 \
+    }                                                                                                             \
+    extern "C" int lib##_profile_collect(void) { return lprof::collect(); }                                       \
+    extern "C" int lib##_profile_entry(int32_t index, const char** name, double* total_ms, int64_t* launches)     \
+    {                                                                                                             \
+        long long n = 0;                                                                                          \
+        const int rc = lprof::entry(index, name, total_ms, &n);                                                   \
+        if (launches) *launches = (int64_t)n;                                                                     \
+        return rc;                                                                                                \
+    }                                                                                                             \
+    extern "C" int lib##_profile_reset(void)                                                                      \
+    {                                                                                                             \
+        lprof::reset();                                                                                           \
+        return 0;                                                                                                 \
+    }
