@@ -10,9 +10,9 @@
 //                              stable radix sort of (tile << 32 | depth) produces; emits, per 8x8 quadrant, a stream
 //                              of splat indices culled with the exact {alpha >= 1/255} ellipse (and the
 //                              reference-format sorted keys / point list in the parity modes)
-//   k_render       per tile  : 4 waves x 8x8 pixels; every wave walks its quadrant's stream through the scalar unit
-//                              (wave-uniform s_loads of index, then of the splat's 48-byte record; software-pipelined,
-//                              no LDS, no barriers) and composites front to back
+//   k_render       per quadrant : one wave x 8x8 pixels; the wave gathers its quadrant's stream 60 records at a time into
+//                              its own LDS stage, a chunk ahead, walks them with broadcast LDS reads (no barriers) and
+//                              composites front to back
 //
 // Behavioural spec: SURVEY.md Appendix A.1-A.3 (the reference's rasterizer is an un-vendored
 // submodule; call site gaussian_renderer/__init__.py:37-52,86-94).  This TU is built with
@@ -38,14 +38,10 @@ __global__ __launch_bounds__(256) void k_preprocess(Settings s, PreprocessArgs a
         for (int t = i; t < a.nb; t += (int)(gridDim.x * blockDim.x)) a.bcount[t] = 0u;
         // the backward's work lists start empty (k_render<true> appends): the image state is a fresh, uninitialised allocation per forward
         if (i < GSR_UNIT_LISTS) a.units[32 * i] = 0u;
-        if (i < GSR_CONT_HDR_WORDS / 32) a.units[cont_hdr_word((size_t)a.tiles) + 32 * i] = 0u;   // (and the continuation area's counters)
-        for (int t = i; t < 4 * a.tiles; t += (int)(gridDim.x * blockDim.x)) a.units[cont_hdr_word((size_t)a.tiles) + GSR_CONT_HDR_WORDS + t] = 0xFFFFFFFFu;
     } else {
         // this frame's tile histogram starts at zero (k_count runs after this kernel)
         for (int t = i; t < a.tiles; t += (int)(gridDim.x * blockDim.x)) a.tile_count[t] = 0u;
         if (i < GSR_UNIT_LISTS) a.units[32 * i] = 0u;   // the backward's work lists start empty (k_render<true> appends)
-        if (i < GSR_CONT_HDR_WORDS / 32) a.units[cont_hdr_word((size_t)a.tiles) + 32 * i] = 0u;   // ... no quadrant is parked for the continuation workgroups, none pulled, no wave has reported
-        for (int t = i; t < 4 * a.tiles; t += (int)(gridDim.x * blockDim.x)) a.units[cont_hdr_word((size_t)a.tiles) + GSR_CONT_HDR_WORDS + t] = 0xFFFFFFFFu;   // (an unwritten list entry)
         if (i == 0) *a.rect_total = 0ull;
         if (a.pstat)   // rank path: the depth-bucket histogram and its fill cursors start at zero as well
             for (int t = i; t < a.nb; t += (int)(gridDim.x * blockDim.x)) { a.bcount[t] = 0u; a.bcursor[t] = 0u; }
@@ -807,41 +803,20 @@ template __global__ void k_tile_sort<GSR_SORT_XL_KEYS, 1024>(uint32_t, uint32_t,
                                                               const unsigned long long*);
 
 // ------------------------------------------------------------------------------------------
-// k_render: front-to-back compositing.  Workgroup = one 16x16 tile = 4 independent waves, wave w
-// owns the 8x8 quadrant (w&1, w>>1) and walks that quadrant's record stream.  The record index is
-// wave-uniform, so the loads below are scalar-unit loads: one 48-byte fetch serves all 64 pixels
-// and the values sit in SGPRs -- no LDS staging, no barriers, each wave stops on its own.
+// k_render: front-to-back compositing.  Workgroup = ONE wave = one 8x8 quadrant: workgroup 4 p + q
+// blends quadrant (q&1, q>>1) of the 16x16 tile at launch position p and walks that quadrant's
+// record stream.  A tile's four walks share nothing; as four waves of one workgroup the slots of
+// the three that finish first would stay taken until the deepest is done.  The wave gathers the
+// stream a chunk of 60 records at a time straight into its own LDS stage (global_load_lds, one
+// chunk ahead of the walk) and reads the records back with broadcast ds_reads into vector
+// registers -- no barriers, each wave stops on its own.
 // ------------------------------------------------------------------------------------------
 #ifdef GSR_EXPERIMENT_TIMELINE   // `make timeline`: per-wave stamps of k_render for tools/bwd_timeline.py
 __device__ unsigned long long gsr_dbg_fwd[4 * 16384];
 extern "C" int gsr_debug_read_fwd(unsigned long long* host, int n) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(gsr_dbg_fwd), (size_t)n * 8); }
 #endif
-// CONT (fast blend only): the CONTINUATION kernel, launched right behind k_render<true, false> (gsr_api.hip).  The forward blend ends when its
-// deepest quadrant's serial walk ends (round 5's timeline: the second half of the kernel is a tail of a few hundred deep walks, each alone on
-// its SIMD at the single-wave issue limit), and which quadrants walk deep is only known once they have: the stream length says little (half of
-// cfg3's streams hold more than 600 entries, ten are WALKED beyond 400).  So a walk that reaches entry s.cont_chunks * GSR_BWD_SEGMENT with
-// pixels still open parks its state -- (T, C, last contributor) of its 64 pixels, 1280 bytes -- and leaves; this kernel's workgroups pull those
-// quadrants and walk the rest of each stream FOUR CHUNKS AT A TIME: wave w takes chunks c0 + w, c0 + w + 4, ... of 60 entries; every chunk but
-// the first is walked from T = 1 (its own transmittance product and colour sum), and the waves hand the true state down the chunks in order
-// through LDS:  T = T_prefix * T_chunk,  C = C_prefix + T_prefix * C_chunk  for a pixel that stays open across the chunk (transmittance only
-// falls, so "T_prefix * T_chunk >= 1e-4" says that no record of the chunk closed it); a pixel that closes INSIDE the chunk is evaluated again,
-// from the true prefix, with the record-parallel pass of the tail mode (one wave scan over the chunk's 60 records) -- every pixel closes once.
-// Which chunks are walked from T = 1 and which from the true state depends on the chunk index and on the open pixels the wave itself saw four
-// chunks earlier, never on timing: the result is the same bits run to run.  Same arithmetic per record as the lone walk; what differs is the
-// association of the products (1e-7 relative), inside the fast blend's tolerance.
-#ifndef GSR_CONT_WAVES
-#define GSR_CONT_WAVES 8   // waves of a workgroup of the continuation KERNEL (CONT == 2) = chunks of a quadrant in flight
-#endif
-#ifndef GSR_EXP_NO_SOLO
-#define GSR_SOLO_THREADS 64
-#else
-#define GSR_SOLO_THREADS 256
-#endif
-template <bool FAST, int CONT, bool INFER>   // INFER: the instance for frames no backward can follow (GsrSettings.forward_only): no last-contributor bookkeeping in the walk
-#ifndef GSR_EXP_LB
-#define GSR_EXP_LB (CONT == 1 ? 5 : 1)   // (only the instance that carries the continuation workgroups needs its register budget capped: their body would take the tiles' walks from five waves per SIMD to four)
-#endif
-__global__ __launch_bounds__(CONT == 2 ? 64 * GSR_CONT_WAVES : (CONT == 0 ? GSR_SOLO_THREADS : 256), GSR_EXP_LB) void k_render(Settings s, const uint32_t* __restrict__ tile_order, const uint32_t* __restrict__ qstart,
+template <bool FAST, bool INFER>   // INFER: the instance for frames no backward can follow (GsrSettings.forward_only): no last-contributor bookkeeping in the walk
+__global__ __launch_bounds__(64) void k_render(Settings s, const uint32_t* __restrict__ tile_order, const uint32_t* __restrict__ qstart,
                                                  const uint32_t* __restrict__ qcount,
                                                  const float4* __restrict__ grec, const uint32_t* __restrict__ qpos,
                                                  const uint32_t* __restrict__ qlist, float* __restrict__ final_T,
@@ -850,8 +825,6 @@ __global__ __launch_bounds__(CONT == 2 ? 64 * GSR_CONT_WAVES : (CONT == 0 ? GSR_
                                                  float* __restrict__ out_color, unsigned long long capacity,
                                                  const unsigned long long* __restrict__ total_dev, uint32_t* __restrict__ units, int tiles)
 {
-    static_assert(FAST || CONT == 0, "continuations belong to the fast blend");
-    static_assert(!INFER || CONT == 0, "the inference instances carry no continuation code");
     const bool fwd_only = INFER || s.forward_only;
     if (*total_dev > capacity) return;
 #ifdef GSR_EXPERIMENT_TIMELINE
@@ -859,37 +832,19 @@ __global__ __launch_bounds__(CONT == 2 ? 64 * GSR_CONT_WAVES : (CONT == 0 ? GSR_
 #endif
     const int W = s.W, H = s.H;
     const int gx = (W + GSR_BLOCK_X - 1) / GSR_BLOCK_X;
-    // the continuation area behind the backward's unit lists (gsr.h: GsrImageLayout.units): header (word 0: quadrants parked so far, word 32: the
-    // continuation workgroups' pull cursor, words 64 + 32 k, k < 16: tile waves that have reported; all zeroed by k_preprocess), the list of parked
-    // quadrants (launch position << 2 | quadrant; ~0 = not yet written: k_preprocess fills it), and 5 x 64 floats of state per quadrant slot
-    const uint32_t ucap = (uint32_t)unit_list_cap((size_t)tiles);
-    uint32_t* const cont_hdr = units + cont_hdr_word((size_t)tiles);
-    uint32_t* const cont_list = cont_hdr + GSR_CONT_HDR_WORDS;
-    float* const cont_state = reinterpret_cast<float*>(cont_list + 4 * (size_t)tiles);
-    const int cont_c = (FAST && s.cont_chunks > 0) ? s.cont_chunks : 0x7fffffff;   // the chunk a lone walk hands over at
-    // SOLO (round 6, the instances without continuation code): ONE wave per workgroup, workgroup 4 p + q = quadrant q of the tile at launch position p.
-    // A tile's four quadrant walks share nothing; as four waves of one workgroup the slots of the three that finish first stay taken until the
-    // deepest is done.
-#ifndef GSR_EXP_NO_SOLO
-    constexpr bool SOLO = CONT == 0;
-#else
-    constexpr bool SOLO = false;
-#endif
-    const int pwave = SOLO ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));       // this wave inside its workgroup
+    const uint32_t ucap = (uint32_t)unit_list_cap((size_t)tiles);   // (gsr.h: GsrImageLayout.units)
     const int lane = threadIdx.x & 63;
-    // per QUADRANT (k_render: once; the continuation kernel: once per pulled quadrant)
-    const bool helper = CONT == 2 || (CONT == 1 && blockIdx.x >= (uint32_t)tiles);   // a continuation workgroup (below): no tile of its own
-    uint32_t lpos = SOLO ? blockIdx.x >> 2 : blockIdx.x;         // the tile's position in the launch order
-    int tile = helper ? 0 : (int)tile_order[lpos];
-    int tile_x = tile % gx, tile_y = tile / gx;
-    int wave = SOLO ? (int)(blockIdx.x & 3u) : pwave;            // the QUADRANT this wave blends (CONT: all four waves the same one)
-    int pxi = tile_x * GSR_BLOCK_X + (wave & 1) * 8 + (lane & 7);
-    int pyi = tile_y * GSR_BLOCK_Y + (wave >> 1) * 8 + (lane >> 3);
-    bool inside = pxi < W && pyi < H;
-    float pixx = (float)pxi, pixy = (float)pyi;
+    const uint32_t lpos = blockIdx.x >> 2;                       // the tile's position in the launch order
+    const int tile = (int)tile_order[lpos];
+    const int tile_x = tile % gx, tile_y = tile / gx;
+    const int wave = (int)(blockIdx.x & 3u);                     // the QUADRANT this wave blends
+    const int pxi = tile_x * GSR_BLOCK_X + (wave & 1) * 8 + (lane & 7);
+    const int pyi = tile_y * GSR_BLOCK_Y + (wave >> 1) * 8 + (lane >> 3);
+    const bool inside = pxi < W && pyi < H;
+    const float pixx = (float)pxi, pixy = (float)pyi;
 
-    int n = helper ? 0 : (int)qcount[4 * tile + wave];
-    uint32_t qs = helper ? 0u : qstart[4 * tile + wave];
+    const int n = (int)qcount[4 * tile + wave];
+    const uint32_t qs = qstart[4 * tile + wave];
     const float4* __restrict__ rec = grec;                      // the per-splat records (48 bytes each)
     const uint32_t* __restrict__ qp = qpos + qs;                // this quadrant's stream of splat indices
 
@@ -1000,70 +955,45 @@ __global__ __launch_bounds__(CONT == 2 ? 64 * GSR_CONT_WAVES : (CONT == 0 ? GSR_
     using Off1 = std::integral_constant<int, RB>;
     int j0 = 0;
     // ---- the walk, records staged through LDS (round 4) ------------------------------------------------------------------------
-    // Through the scalar unit (above, kept for A/B builds) a batch's records can only be requested ONE batch ahead -- scalar loads
+    // Through the scalar unit a batch's records can only be requested ONE batch ahead -- scalar loads
     // return out of order, so the only wait is lgkmcnt(0), which also waits for whatever was issued last -- and a request takes ~300 ns
     // (K-cache miss -> L2): the deepest quadrant's walk, which IS the kernel's duration, ran at 107 ns per record whether a record cost 40
     // instructions or 32 (measured: RB = 2 -> 85 us, RB = 3 -> 72 us).  Here the wave gathers a whole CHUNK of 60 records with
-    // vector loads (lane l: entry 60 c + l, three 16-byte loads), one chunk ahead of the walk, parks them in its own 2 x 2880 bytes of
+    // vector loads (lane l: entry 60 c + l, three 16-byte loads), one chunk ahead of the walk, into its own 2 x 3072 bytes of
     // LDS and walks them with broadcast ds_read_b128: LDS returns in order (the compiler counts lgkmcnt exactly, a batch ahead costs
     // nothing), takes ~50 ns instead of ~300, and the record's fields arrive in VECTOR registers -- a VALU instruction with a scalar
     // operand issues at half rate on gfx950 (tools/valu_peak.hip), so the per-record arithmetic gets cheaper for the crowded SIMDs too.
     // Chunks are the backward's segments: the checkpoint test sits at the chunk boundary.
     constexpr int CH = GSR_BWD_SEGMENT;
     static_assert(CH <= GSR_WAVE && CH % (2 * RB) == 0, "a chunk is one gather of the wave and a whole number of double batches");
-    constexpr int NWV = CONT == 2 ? GSR_CONT_WAVES : (SOLO ? 1 : 4);   // waves per workgroup
-    // DIRECT (round 6, the instances without continuation code): the gather goes straight into LDS (global_load_lds_dwordx4: lane l's 16 bytes land at
-    // base + 16 l, so a chunk is staged as three planes of 64 float4 -- part k of record j at [64 k + j]) instead of through twelve vector
-    // registers that stay live across the whole walk of the chunk before; nothing is parked.
-#ifndef GSR_EXP_NO_DIRECT
-    constexpr bool DIRECT = CONT == 0;
-#else
-    constexpr bool DIRECT = false;
-#endif
-    constexpr int STAGE_F4 = DIRECT ? 3 * GSR_WAVE : CH * 3 + 3;   // (+3: the walk's read-ahead of a chunk's last double batch ends one batch past the chunk -- harmless, never used, but it has to be inside the allocation; DIRECT: the planes hold 64 entries)
-    constexpr int RS = DIRECT ? 16 : 48;                           // bytes from a record to the next in the stage
-    constexpr int P1 = DIRECT ? 16 * GSR_WAVE : 16, P2 = DIRECT ? 32 * GSR_WAVE : 32;   // ... and to a record's second and third part
-    constexpr int BB = RB * RS;                                    // bytes per batch
-    __shared__ float4 stage_all[NWV][2][STAGE_F4];
-    float4(*const stage)[STAGE_F4] = stage_all[pwave];
-    float4 g0, g1, g2;   // (not DIRECT) the chunk in flight: this lane's record
-    uint32_t nidx = 0;   // DIRECT: this lane's stream entry of the chunk to be gathered NEXT, fetched a chunk ahead (the record loads depend on it: fetched
-                         // where it is needed, every chunk boundary waits out one more round trip to memory)
-    if constexpr (DIRECT) nidx = n > 0 ? qp[min(lane, n - 1)] : 0u;
-    auto gather = [&](int c) {   // entries past the end re-read the last one (never walked); lanes CH.. load too (never parked)
-        const size_t idx = DIRECT ? (size_t)nidx : (size_t)qp[min(c * CH + lane, n - 1)];
-        if constexpr (DIRECT) {
-            typedef const __attribute__((address_space(1))) void* gptr;
-            typedef __attribute__((address_space(3))) void* lptr;
-            const float4* p = rec + 3 * idx;
-            nidx = qp[min((c + 1) * CH + lane, n - 1)];
-            __builtin_amdgcn_global_load_lds((gptr)(p + 0), (lptr)&stage[c & 1][0], 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gptr)(p + 1), (lptr)&stage[c & 1][GSR_WAVE], 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gptr)(p + 2), (lptr)&stage[c & 1][2 * GSR_WAVE], 16, 0, 0);
-        } else {
-            g0 = rec[3 * idx + 0];
-            g1 = rec[3 * idx + 1];
-            g2 = rec[3 * idx + 2];
-        }
+    // The gather goes straight into LDS (round 6; global_load_lds_dwordx4: lane l's 16 bytes land at base + 16 l, so a chunk is staged as
+    // three planes of 64 float4 -- part k of record j at [64 k + j]) instead of through twelve vector registers that stay live across the
+    // whole walk of the chunk before.
+    constexpr int STAGE_F4 = 3 * GSR_WAVE;                   // (the planes hold 64 entries: the walk's read-ahead of a chunk's last double batch ends one batch past the chunk -- harmless, never used, inside the allocation)
+    constexpr int RS = 16;                                   // bytes from a record to the next in the stage
+    constexpr int P1 = 16 * GSR_WAVE, P2 = 32 * GSR_WAVE;    // ... and to a record's second and third part
+    constexpr int BB = RB * RS;                              // bytes per batch
+    __shared__ float4 stage[2][STAGE_F4];
+    // this lane's stream entry of the chunk to be gathered NEXT, fetched a chunk ahead (the record loads depend on it: fetched where it is
+    // needed, every chunk boundary waits out one more round trip to memory)
+    uint32_t nidx = n > 0 ? qp[min(lane, n - 1)] : 0u;
+    auto gather = [&](int c) {   // entries past the end re-read the last one (never walked); lanes CH.. load too (never walked)
+        typedef const __attribute__((address_space(1))) void* gptr;
+        typedef __attribute__((address_space(3))) void* lptr;
+        const float4* p = rec + 3 * (size_t)nidx;
+        nidx = qp[min((c + 1) * CH + lane, n - 1)];
+        __builtin_amdgcn_global_load_lds((gptr)(p + 0), (lptr)&stage[c & 1][0], 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr)(p + 1), (lptr)&stage[c & 1][GSR_WAVE], 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr)(p + 2), (lptr)&stage[c & 1][2 * GSR_WAVE], 16, 0, 0);
     };
-    auto landed = [&]() {   // DIRECT: everything gathered so far is in LDS
-        if constexpr (DIRECT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    };
-    auto park = [&](int c) {
-        if constexpr (!DIRECT) {
-            if (lane < CH) {
-                float4* d = &stage[c & 1][3 * lane];
-                d[0] = g0; d[1] = g1; d[2] = g2;
-            }
-        }
-    };
+    auto landed = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };   // everything gathered so far is in LDS
     // A batch's records come out of LDS with ds_read_b128 / ds_read_b64 at a wave-uniform address (broadcast), issued from inline
     // assembly: the reads have to be ISSUED a batch ahead of their use, behind the blend that frees their registers, and left to the
     // compiler they all end up at the top of the loop body (the fetched batch copied aside, the LDS waited for with nothing to do;
     // volatile loads turn into flat loads).  LDS returns in order, so `ready` waits with the exact count of reads issued since.
     // Rules that keep this sound: every `issue` is followed by a `ready` on the same registers before they die (the compiler
     // believes they were written at the issue), and nothing else of this wave is in flight on lgkmcnt inside the loop (no scalar
-    // loads, no compiler-made LDS access: the parks sit between chunks, behind a full wait).
+    // loads, no compiler-made LDS access).
     typedef float v4f __attribute__((ext_vector_type(4)));
 #ifdef GSR_EXP_HI_TEST
     typedef float v2f __attribute__((ext_vector_type(2)));
@@ -1112,8 +1042,7 @@ __global__ __launch_bounds__(CONT == 2 ? 64 * GSR_CONT_WAVES : (CONT == 0 ? GSR_
     using Behind9 = std::integral_constant<int, 9>;
     using Behind0 = std::integral_constant<int, 0>;
 
-    // ---- the record-parallel pass of the fast blend (tail mode; the continuation kernel's re-evaluation of a pixel that closes inside a
-    // chunk): lanes = the records c0 + lane of ONE chunk (r0, r1, r2; `valid`), the pixels of `todo` take turns two at a time.
+    // ---- the record-parallel pass of the fast blend (tail mode): lanes = the records c0 + lane of ONE chunk (r0, r1, r2; `valid`), the pixels of `todo` take turns two at a time.
     // T_j = T_p * prod_{i<=j} (1 - alpha_i) is one inclusive wave scan (transmittance only falls: "T >= 1e-4" is a prefix mask, the
     // pixel closes at its first failing lane), the colour is three wave sums of c * alpha * T_before; no loop over the hits.
     // Updates (Tw, C, last_q) of the pixels' own lanes; returns the pixels of `todo` that closed.
@@ -1238,237 +1167,6 @@ __global__ __launch_bounds__(CONT == 2 ? 64 * GSR_CONT_WAVES : (CONT == 0 ? GSR_
         }
     };
 
-    if constexpr (CONT != 0) {
-    if (helper) {
-        // ================= continuation workgroups: parked quadrants, four chunks in flight =========================================================
-        // CONT == 1: the LAST workgroups of k_render's own grid (dispatched behind every tile's workgroup, so they never keep one from starting):
-        // they wait for quadrants to be parked while the tiles' walks are still running and leave when every tile wave has reported and the list is
-        // drained.  CONT == 2: a kernel of its own behind k_render<true, 0> (everything is parked by then; nothing waits).
-        __shared__ uint32_t s_pull;          // the parked quadrant this workgroup works on (~0: none left)
-        __shared__ uint32_t s_seq;           // the chunk whose prefix state lies in s_hand (~0: the quadrant is finished)
-        __shared__ uint32_t s_pending;       // re-evaluations of closing pixels still on their way to s_fin
-        __shared__ float s_hand[5][64];      // (T signed as Tw, C0, C1, C2, last_q) of the 64 pixels before that chunk's first entry
-        __shared__ float s_fin[5][64];       // the same five values of every pixel that has CLOSED (written once, by the wave that saw it close)
-        const size_t HWc = (size_t)H * W;
-        const uint32_t hidx = CONT == 1 ? blockIdx.x - (uint32_t)tiles : blockIdx.x, nhelp = CONT == 1 ? gridDim.x - (uint32_t)tiles : gridDim.x;
-        bool first_pull = true;
-        for (;;) {
-            __syncthreads();                 // every wave is done with the previous quadrant (s_seq, s_hand, s_fin, the stages)
-            if (threadIdx.x == 0) {
-                // the first pull is the workgroup's own index (no atomic: 768 returning atomics on one word are 9 us of queueing), the later ones
-                // come from the shared cursor behind those
-                const uint32_t ei = first_pull ? hidx : nhelp + atomicAdd(cont_hdr + 32, 1u);
-                uint32_t ent = 0xFFFFFFFFu;
-                if (ei < 4u * (uint32_t)tiles) {
-                    if constexpr (CONT == 2) {
-                        if (ei < cont_hdr[0]) ent = cont_list[ei];
-                    } else {
-                        // wait for entry ei of the list, or for the proof that it will never come: every tile wave reports (after its own post, if it
-                        // made one) on one of 16 counters; once they all have and the entry is still empty, the list ended below it
-                        for (uint32_t spins = 0; spins < (1u << 24); ++spins) {
-                            ent = __hip_atomic_load(cont_list + ei, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            if (ent != 0xFFFFFFFFu) break;
-                            if ((spins & 7u) == 7u) {
-                                uint32_t reported = 0;
-                                for (int k = 0; k < 16; ++k) reported += __hip_atomic_load(cont_hdr + 64 + 32 * k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                if (reported >= 4u * (uint32_t)tiles) {
-                                    ent = __hip_atomic_load(cont_list + ei, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                    break;
-                                }
-                            }
-                            __builtin_amdgcn_s_sleep(8);
-                        }
-                    }
-                }
-                s_pull = ent;
-                s_seq = (uint32_t)cont_c;
-                s_pending = 0u;
-            }
-            first_pull = false;
-            __syncthreads();
-            const uint32_t ent = s_pull;
-            if (ent == 0xFFFFFFFFu) return;
-            lpos = ent >> 2;
-            wave = (int)(ent & 3u);
-            tile = (int)tile_order[lpos];
-            tile_x = tile % gx; tile_y = tile / gx;
-            pxi = tile_x * GSR_BLOCK_X + (wave & 1) * 8 + (lane & 7);
-            pyi = tile_y * GSR_BLOCK_Y + (wave >> 1) * 8 + (lane >> 3);
-            inside = pxi < W && pyi < H;
-            pixx = (float)pxi; pixy = (float)pyi;
-            n = (int)qcount[4 * tile + wave];
-            qs = qstart[4 * tile + wave];
-            qp = qpos + qs;
-            const int pix_id = inside ? W * pyi + pxi : 0;
-            {
-                const float* st = cont_state + (size_t)(4 * tile + wave) * GSR_CONT_STATE_FLOATS;
-                if constexpr (CONT == 1) {   // parked by a wave of THIS launch with write-through stores: read past this CU's L1
-                    Tw = __hip_atomic_load(st + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    C0 = __hip_atomic_load(st + 64 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    C1 = __hip_atomic_load(st + 128 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    C2 = __hip_atomic_load(st + 192 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    last_q = __hip_atomic_load(reinterpret_cast<const uint32_t*>(st) + 256 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                } else {
-                    Tw = st[lane]; C0 = st[64 + lane]; C1 = st[128 + lane]; C2 = st[192 + lane];
-                    last_q = reinterpret_cast<const uint32_t*>(st)[256 + lane];
-                }
-            }
-            auto to_fin = [&]() {   // this lane's pixel has closed: its five values, for whoever finishes the quadrant
-                s_fin[0][lane] = Tw; s_fin[1][lane] = C0; s_fin[2][lane] = C1; s_fin[3][lane] = C2; s_fin[4][lane] = __uint_as_float(last_q);
-            };
-            if (pwave == 0) to_fin();        // (the pixels that were closed when the quadrant was parked; the open ones are rewritten when they close)
-            __syncthreads();
-            const int c_first = cont_c, nchunks = (n + CH - 1) / CH;
-            unsigned long long myopen = __ballot(Tw > 0.0f);   // the open pixels as this wave last saw them
-            bool have_g = false;
-            for (int c = c_first + pwave; c < nchunks; c += NWV) {
-                if (__hip_atomic_load(&s_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0xFFFFFFFFu) break;   // finished further up: nothing to add
-                const int m = min(CH, n - c * CH);   // records of this chunk
-                if (!have_g) gather(c);
-                park(0);
-                asm volatile("" ::: "memory");
-                have_g = c + NWV < nchunks;
-                if (have_g) gather(c + NWV);         // in flight behind this chunk's walk
-                // wait for the state before this chunk's first entry; false: the quadrant finished further up
-                auto wait_prefix = [&]() {
-                    for (uint32_t spins = 0; spins < (1u << 22); ++spins) {   // (the chunk below is always on its way: the bound only keeps a logic error from hanging the device)
-                        const uint32_t v = __hip_atomic_load(&s_seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        if (v == 0xFFFFFFFFu) return false;
-                        if (v >= (uint32_t)c) return true;
-                        __builtin_amdgcn_s_sleep(1);
-                    }
-                    return false;
-                };
-                const bool first = c == c_first;
-                const bool spec = !first && __builtin_popcountll(myopen) > TAIL_LANES;
-                bool walk = spec;
-                if (spec) {
-                    // walked from T = 1 (pixels this wave knows to be closed: from 0) while the chunks below are still on their way
-                    Tw = ((myopen >> lane) & 1ull) ? 1.0f : 0.0f;
-                    C0 = 0.f; C1 = 0.f; C2 = 0.f;
-                    lq = 0; j0 = c * CH;
-                } else {
-                    if (!first) {
-                        if (!wait_prefix()) break;
-                        Tw = s_hand[0][lane]; C0 = s_hand[1][lane]; C1 = s_hand[2][lane]; C2 = s_hand[3][lane];
-                        last_q = __float_as_uint(s_hand[4][lane]);
-                    }
-                    myopen = __ballot(Tw > 0.0f);
-                    walk = __builtin_popcountll(myopen) > TAIL_LANES;   // (only the first chunk can get here with many pixels open)
-                    j0 = c * CH;
-                    lq = (int)last_q - j0;
-                }
-                if (walk) {
-                    // the chunk's records, one batch of three per read, a double batch per step (the lone walk's loop without its tests: pixels that are
-                    // closed are inert by construction)
-                    RecV VA, VB;
-                    Rec4 A, B;
-                    uint32_t addr = lds0;
-                    GSR_ISSUE(addr, 0, VA);
-                    int k = 0;
-                    while (k + 2 * RB <= m) {
-                        GSR_ISSUE(addr, BB, VB);
-                        ready(VA, Behind9{}, A);
-                        blend4(j0, A, std::false_type{}, Off0{});
-                        GSR_ISSUE(addr, 2 * BB, VA);
-                        ready(VB, Behind9{}, B);
-                        blend4(j0 + RB, B, std::false_type{}, Off1{});
-                        addr += 2 * BB;
-                        j0 += 2 * RB;
-                        lq -= 2 * RB;
-                        k += 2 * RB;
-                    }
-                    ready(VA, Behind0{}, A);
-                    if (k < m) {   // the stream ends inside this chunk: one or two bounds-tested batches (A holds the first)
-                        blend4(j0, A, std::true_type{}, Off0{});
-                        j0 += RB;
-                        lq -= RB;
-                        if (j0 < n) {
-                            GSR_ISSUE(addr, BB, VB);
-                            ready(VB, Behind0{}, B);
-                            blend4(j0, B, std::true_type{}, Off0{});
-                            j0 += RB;
-                            lq -= RB;
-                        }
-                    }
-                }
-                unsigned long long todo;         // pixels to evaluate with the record-parallel pass, from the TRUE state in their lanes
-                const unsigned long long open_before = myopen;
-                bool last;                        // the state after this chunk is the quadrant's result
-                if (spec) {
-                    const float Tl = Tw, L0 = C0, L1 = C1, L2 = C2;
-                    const uint32_t hit = (uint32_t)(lq + j0);                       // > c * CH: the chunk's last contributor of this pixel
-                    if (!wait_prefix()) break;
-                    const float Tp = s_hand[0][lane], P0 = s_hand[1][lane], P1 = s_hand[2][lane], P2 = s_hand[3][lane];
-                    const uint32_t lqp = __float_as_uint(s_hand[4][lane]);
-                    const bool open_p = Tp > 0.0f;
-                    const float Tt = Tp * Tl;
-                    const bool thru = open_p && Tl > 0.0f && Tt >= 0.0001f;       // open before the chunk and no record of it closes the pixel
-                    todo = __ballot(open_p && !thru);                              // these close inside the chunk
-                    myopen = __ballot(thru);
-                    last = myopen == 0ull || c == nchunks - 1;
-                    if (!last) {
-                        // the chunks above only need to know WHICH pixels are still open: the state goes down the chain before the closing pixels
-                        // are evaluated (their values go to s_fin, off the chain)
-                        if (todo && lane == 0) __hip_atomic_fetch_add(&s_pending, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        s_hand[0][lane] = thru ? Tt : -1.0f;
-                        s_hand[1][lane] = __builtin_fmaf(Tp, L0, P0); s_hand[2][lane] = __builtin_fmaf(Tp, L1, P1); s_hand[3][lane] = __builtin_fmaf(Tp, L2, P2);
-                        s_hand[4][lane] = __uint_as_float(hit > (uint32_t)(c * CH) ? hit : lqp);
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                        if (lane == 0) __hip_atomic_store(&s_seq, (uint32_t)(c + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        if (!fwd_only && c + 1 <= GSR_BWD_SEGMENTS - 1 && inside && thru)   // (the backward reads a checkpoint only where the pixel goes on)
-                            ck[(size_t)c * HWc + pix_id] = make_float4(Tt, __builtin_fmaf(Tp, L0, P0), __builtin_fmaf(Tp, L1, P1), __builtin_fmaf(Tp, L2, P2));
-                    }
-                    Tw = thru ? Tt : Tp;
-                    C0 = thru ? __builtin_fmaf(Tp, L0, P0) : P0;
-                    C1 = thru ? __builtin_fmaf(Tp, L1, P1) : P1;
-                    C2 = thru ? __builtin_fmaf(Tp, L2, P2) : P2;
-                    last_q = (thru && hit > (uint32_t)(c * CH)) ? hit : lqp;
-                } else {
-                    if (walk) last_q = (uint32_t)(lq + j0);
-                    todo = walk ? 0ull : myopen;
-                }
-                if (todo) {   // records across the lanes, the pixels two at a time
-                    const float4* sp = &stage[0][3 * min(lane, CH - 1)];
-                    (void)tail_pairs(todo, c * CH, lane < m, sp[0], sp[1], sp[2]);
-                }
-                if (spec) {
-                    if (todo) {
-                        if ((todo >> lane) & 1ull) to_fin();
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                        if (!last && lane == 0) __hip_atomic_fetch_sub(&s_pending, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    }
-                } else {
-                    myopen = __ballot(Tw > 0.0f);
-                    if (((open_before & ~myopen) >> lane) & 1ull) to_fin();   // closed in this chunk
-                    last = myopen == 0ull || c == nchunks - 1;
-                    if (!last) {
-                        if (!fwd_only && c + 1 <= GSR_BWD_SEGMENTS - 1 && inside)
-                            ck[(size_t)c * HWc + pix_id] = make_float4(__builtin_fabsf(Tw), C0, C1, C2);
-                        s_hand[0][lane] = Tw; s_hand[1][lane] = C0; s_hand[2][lane] = C1; s_hand[3][lane] = C2; s_hand[4][lane] = __uint_as_float(last_q);
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                        if (lane == 0) __hip_atomic_store(&s_seq, (uint32_t)(c + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    }
-                }
-                if (last) {
-                    // every pixel that closed on the way left its values in s_fin (the waves still evaluating theirs are counted in s_pending)
-                    for (uint32_t spins = 0; spins < (1u << 22); ++spins) {
-                        if (__hip_atomic_load(&s_pending, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u) break;
-                        __builtin_amdgcn_s_sleep(1);
-                    }
-                    if (!(Tw > 0.0f)) {
-                        Tw = s_fin[0][lane]; C0 = s_fin[1][lane]; C1 = s_fin[2][lane]; C2 = s_fin[3][lane];
-                        last_q = __float_as_uint(s_fin[4][lane]);
-                    }
-                    finish();
-                    if (lane == 0) __hip_atomic_store(&s_seq, 0xFFFFFFFFu, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    break;
-                }
-            }
-        }
-    }
-    }
-    {
     auto keep_going = [&](int jb) {
         const unsigned long long open_mask = __ballot(Tw > 0.0f);
         int open;    // (through asm: the compiler widens popcountll's comparison to 64 bits and then does it on the VECTOR unit)
@@ -1496,48 +1194,15 @@ __global__ __launch_bounds__(CONT == 2 ? 64 * GSR_CONT_WAVES : (CONT == 0 ? GSR_
             next_ck += GSR_BWD_SEGMENT;
         }
     };
-    // a lone walk that reaches the hand-over chunk parks its state for the continuation kernel and leaves (nothing of the quadrant's
-    // outputs is written here; the checkpoint before the chunk has been)
-    auto park_quadrant = [&](uint32_t lastq_abs) {
-        int slot = 4 * tile + wave;
-        asm volatile("" : "+s"(slot));   // (the addresses are formed HERE: hoisted out of the walk they cost it eight vector registers and a wave per SIMD)
-        float* st = cont_state + (size_t)slot * GSR_CONT_STATE_FLOATS;
-        if constexpr (CONT == 1) {
-            // read by a workgroup of THIS launch, on any XCD: write-through stores, drained, then the list entry (MI355X_MICROARCH.md, hand-off forms)
-            __hip_atomic_store(st + lane, Tw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(st + 64 + lane, C0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(st + 128 + lane, C1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(st + 192 + lane, C2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(reinterpret_cast<uint32_t*>(st) + 256 + lane, lastq_abs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (lane == 0) {
-                const uint32_t at = atomicAdd(cont_hdr, 1u);
-                __hip_atomic_store(cont_list + at, lpos << 2 | (uint32_t)wave, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the entry is out before this wave reports: a waiting workgroup that has seen every report has seen every entry)
-            }
-        } else {
-            st[lane] = Tw; st[64 + lane] = C0; st[128 + lane] = C1; st[192 + lane] = C2;
-            reinterpret_cast<uint32_t*>(st)[256 + lane] = lastq_abs;
-            if (lane == 0) cont_list[atomicAdd(cont_hdr, 1u)] = lpos << 2 | (uint32_t)wave;
-        }
-    };
-    auto report = [&]() {   // CONT == 1: this tile wave is done (parked or finished): one of 16 counters the waiting continuation workgroups add up
-        if constexpr (CONT == 1) {
-            if (lane == 0) (void)__hip_atomic_fetch_add(cont_hdr + 64 + 32 * (blockIdx.x & 15u), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    };
-    bool hand_over = false;   // the walk reached the hand-over chunk with the stream going on
     if (n > 0) {
         gather(0);
         landed();
-        park(0);
         if (n > CH) gather(1);
         bool go = true;
         for (int c = 0;; ++c) {
             const int b = c & 1;
             const int m = min(CH, n - c * CH);   // records of this chunk
             checkpoint(j0);                      // j0 == c * CH: the state before the chunk's first entry
-            if (FAST && c == cont_c) { hand_over = true; break; }
             RecV VA, VB;
             Rec4 A, B;
             uint32_t addr = b ? lds1 : lds0;
@@ -1586,17 +1251,11 @@ __global__ __launch_bounds__(CONT == 2 ? 64 * GSR_CONT_WAVES : (CONT == 0 ? GSR_
                 }
             }
             if (!go || j0 >= n) break;
-            landed();   // (DIRECT: chunk c + 1 is in its buffer; the gather below goes into the buffer this chunk has just been walked out of)
-            park(c + 1);
+            landed();   // (chunk c + 1 is in its buffer; the gather below goes into the buffer this chunk has just been walked out of)
             if ((c + 2) * CH < n) gather(c + 2);
         }
     }
     last_q = (uint32_t)(lq + j0);   // (lq + j0 >= 0: a pixel without a hit kept lq = -j0)
-    if (hand_over) {
-        park_quadrant(last_q);
-        report();
-        return;
-    }
 
     if (j0 < n) checkpoint(j0);   // the walk stopped exactly on a checkpoint entry (tail mode takes over from here)
 #ifdef GSR_EXPERIMENT_TIMELINE
@@ -1614,11 +1273,6 @@ __global__ __launch_bounds__(CONT == 2 ? 64 * GSR_CONT_WAVES : (CONT == 0 ? GSR_
         unsigned long long open_mask = __ballot(Tw > 0.0f);
         int c0 = j0;
         while (c0 < n && open_mask) {
-            if (c0 % CH == 0 && c0 / CH == cont_c) {   // (the tail's chunks end on checkpoint entries: the hand-over entry is the top of one)
-                park_quadrant(last_q);
-                report();
-                return;
-            }
             const int c1 = min(n, (c0 / GSR_BWD_SEGMENT + 1) * GSR_BWD_SEGMENT);   // the chunk ends where the next checkpoint sits (<= 60 entries)
             const int j = c0 + lane;
             const bool valid = j < c1;
@@ -1703,21 +1357,15 @@ __global__ __launch_bounds__(CONT == 2 ? 64 * GSR_CONT_WAVES : (CONT == 0 ? GSR_
     }
 #endif
     finish();
-    report();
-    }   // (a tile's workgroup)
 }
 
-template __global__ void k_render<false, 0, false>(Settings, const uint32_t*, const uint32_t*, const uint32_t*, const float4*, const uint32_t*, const uint32_t*, float*, uint32_t*,
+template __global__ void k_render<false, false>(Settings, const uint32_t*, const uint32_t*, const uint32_t*, const float4*, const uint32_t*, const uint32_t*, float*, uint32_t*,
                                                 uint32_t*, float*, float4*, float*, unsigned long long, const unsigned long long*, uint32_t*, int);
-template __global__ void k_render<true, 0, false>(Settings, const uint32_t*, const uint32_t*, const uint32_t*, const float4*, const uint32_t*, const uint32_t*, float*, uint32_t*,
+template __global__ void k_render<true, false>(Settings, const uint32_t*, const uint32_t*, const uint32_t*, const float4*, const uint32_t*, const uint32_t*, float*, uint32_t*,
                                                 uint32_t*, float*, float4*, float*, unsigned long long, const unsigned long long*, uint32_t*, int);
-template __global__ void k_render<true, 2, false>(Settings, const uint32_t*, const uint32_t*, const uint32_t*, const float4*, const uint32_t*, const uint32_t*, float*, uint32_t*,
+template __global__ void k_render<false, true>(Settings, const uint32_t*, const uint32_t*, const uint32_t*, const float4*, const uint32_t*, const uint32_t*, float*, uint32_t*,
                                                 uint32_t*, float*, float4*, float*, unsigned long long, const unsigned long long*, uint32_t*, int);
-template __global__ void k_render<true, 1, false>(Settings, const uint32_t*, const uint32_t*, const uint32_t*, const float4*, const uint32_t*, const uint32_t*, float*, uint32_t*,
-                                                uint32_t*, float*, float4*, float*, unsigned long long, const unsigned long long*, uint32_t*, int);
-template __global__ void k_render<false, 0, true>(Settings, const uint32_t*, const uint32_t*, const uint32_t*, const float4*, const uint32_t*, const uint32_t*, float*, uint32_t*,
-                                                uint32_t*, float*, float4*, float*, unsigned long long, const unsigned long long*, uint32_t*, int);
-template __global__ void k_render<true, 0, true>(Settings, const uint32_t*, const uint32_t*, const uint32_t*, const float4*, const uint32_t*, const uint32_t*, float*, uint32_t*,
+template __global__ void k_render<true, true>(Settings, const uint32_t*, const uint32_t*, const uint32_t*, const float4*, const uint32_t*, const uint32_t*, float*, uint32_t*,
                                                 uint32_t*, float*, float4*, float*, unsigned long long, const unsigned long long*, uint32_t*, int);
 
 // ------------------------------------------------------------------------------------------

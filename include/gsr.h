@@ -224,9 +224,7 @@ typedef struct GsrImageLayout {
                           of the wave) mod GSR_UNIT_LISTS: the counters first (word 32 l = list l's, a 128-byte line each; zeroed by the frame's first kernel), then the lists, `cap` slots
                           each (the mapping wave -> list is static, so `cap` cannot overflow).  The backward's waves (one-wave workgroups, round 6) take the units of list
                           (wave id mod GSR_UNIT_LISTS) in turn, from the list's END -- the deep quadrants are appended last and would be the kernel's tail --: no
-                          wave is launched for a (tile, segment) pair nothing reaches (four of five workgroups were, round 3).  Behind the lists (round 6, GSR_CONT_CHUNKS > 0 only):
-                          the forward blend's continuation area -- counters, the list of quadrants whose walk was parked at entry
-                          GSR_CONT_CHUNKS * GSR_BWD_SEGMENT, 1280 bytes of parked state per quadrant (csrc/gsr_forward.hip: k_render<true, 1 / 2>)  */
+                          wave is launched for a (tile, segment) pair nothing reaches (four of five workgroups were, round 3).  */
     size_t total;
 } GsrImageLayout;
 

@@ -89,6 +89,19 @@ def test_layouts_are_disjoint_and_aligned():
     assert lib.gsr_geom_layout(-1, C.byref(gl)) < 0 and b"bad arguments" in lib.gsr_last_error()
 
 
+@pytest.mark.parametrize("width,height", [(802, 550), (17, 9)])
+def test_image_state_ends_with_the_unit_lists(width, height):
+    """`units` is the last field of the image state and holds the backward's work lists and nothing else (include/gsr.h: GsrImageLayout.units):
+    64 counters of a 128-byte line each, then 64 lists of ceil(4 tiles / 64) * 10 entries; fields start on 256 bytes and `total` carries 256 spare."""
+    from gaussianavatars_amd import _lib
+
+    il = _lib.GsrImageLayout()
+    assert _lib.gsr().gsr_image_layout(width, height, C.byref(il)) == 0
+    tiles = ((width + 15) // 16) * ((height + 15) // 16)
+    extent = 4 * (32 * 64 + 64 * ((4 * tiles + 63) // 64) * 10)
+    assert il.units % 256 == 0 and il.total - 256 - il.units == (extent + 255) // 256 * 256
+
+
 def _check(segs, total):
     segs = sorted(segs)
     for (o, n), (o2, _) in zip(segs, segs[1:]):

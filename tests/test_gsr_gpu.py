@@ -223,6 +223,28 @@ def test_zero_splats_renders_background():
     assert torch.equal(color, bg[:, None, None].expand(3, 37, 53))
 
 
+@pytest.mark.parametrize("fast", [True, False])
+def test_zero_splats_forward_and_backward_in_both_blend_modes(fast):
+    """P == 0 is the one frame whose state the host zeroes itself (no k_preprocess workgroup runs): the image is the background bit for bit in
+    both blend modes, radii is empty, and a backward through it returns."""
+    from gaussianavatars_amd.rasterizer import GaussianRasterizationSettings, GaussianRasterizer, set_fast_blend
+
+    dev = _dev()
+    z = lambda *s: torch.zeros(*s, device=dev, requires_grad=True)
+    bg = torch.tensor([0.25, 0.5, 0.75], device=dev)
+    eye = torch.eye(4, device=dev)
+    rs = GaussianRasterizationSettings(32, 48, 0.5, 0.5, bg, 1.0, eye, eye, 0, torch.zeros(3, device=dev), False, False)
+    prev = set_fast_blend(fast)
+    try:
+        color, radii = GaussianRasterizer(rs)(means3D=z(0, 3), means2D=z(0, 3), opacities=z(0, 1), shs=z(0, 1, 3), scales=z(0, 3), rotations=z(0, 4))
+        color.sum().backward()
+        torch.cuda.synchronize()
+    finally:
+        set_fast_blend(prev)
+    assert radii.numel() == 0
+    assert torch.equal(color.detach(), bg[:, None, None].expand(3, 32, 48))
+
+
 def test_replay_on_capacity_overflow(oracle):
     """A frame needing more instances than the current capacity hint is replayed, not truncated."""
     from gaussianavatars_amd import rasterizer as R
