@@ -461,3 +461,56 @@ def grl():
 grl_error = partial(last_error, "grl")
 grl_profile_enable = partial(profile_enable, ("grl",))
 grl_profile_read = partial(profile_read, ("grl",))
+
+
+# ------------------------------------------------------------------------------------------------
+# libgdc_hip.so : adaptive density control (include/gdc.h).  Loaded only by densify.py, at the first densification on device tensors.
+# ------------------------------------------------------------------------------------------------
+#: tag -> LibSpec of the libraries added after LIBS was pinned to its six tags (tests/test_lib_loader_cpu.py); handle(), last_error() and the
+#: profile shims take these tags exactly like those of LIBS, and build() checks both tables
+MORE_LIBS = {}
+
+GDC_LIB_PATH = _lib_path("gdc")
+GDC_ABI_VERSION = 1
+GDC_CHUNK = 256                # include/gdc.h: splats per workgroup of the scan
+GDC_MAX_TENSORS = 24           # include/gdc.h: tensors one gather launch moves
+GDC_MAX_SPLATS = 1 << 30       # include/gdc.h: P must stay below this
+GDC_COPY, GDC_MOMENT, GDC_ZERO, GDC_XYZ, GDC_SCALING = range(5)   # include/gdc.h: GdcTensor.kind
+
+
+class GdcParams(C.Structure):
+    """include/gdc.h: GdcParams"""
+    _fields_ = [("max_grad", C.c_float), ("min_opacity", C.c_float), ("extent", C.c_float), ("percent_dense", C.c_float),
+                ("max_screen_size", C.c_float)]
+
+
+class GdcTensor(C.Structure):
+    """include/gdc.h: GdcTensor"""
+    _fields_ = [("src", _P), ("dst", _P), ("row_floats", C.c_int32), ("kind", C.c_int32)]
+
+
+GDC_SYMBOLS = {
+    "gdc_abi_version": (C.c_int, []),
+    "gdc_last_error": (C.c_char_p, []),
+    "gdc_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "gdc_plan": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(GdcParams), _P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, C.POINTER(C.c_int32), _P]),
+    "gdc_emit": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(GdcTensor), _P, _P, _P, _P, _P, C.c_int32, _P, _P, _P,
+                           _P, _P]),
+    **_profile_symbols("gdc"),
+}
+
+MORE_LIBS["gdc"] = LibSpec("gdc", GDC_LIB_PATH, GDC_SYMBOLS, GDC_ABI_VERSION)
+_gdc = None
+
+
+def gdc():
+    """The density-control library; raises (never falls back) when it is not built."""
+    global _gdc
+    if _gdc is None:
+        _gdc = _load(MORE_LIBS["gdc"])
+    return _gdc
+
+
+gdc_error = partial(last_error, "gdc")
+gdc_profile_enable = partial(profile_enable, ("gdc",))
+gdc_profile_read = partial(profile_read, ("gdc",))

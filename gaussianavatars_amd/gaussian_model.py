@@ -9,8 +9,11 @@ reference's classes in a checkout (`patch_reference()`).  `binding_impl="unfused
 fused kernels (the A/B leg of bench.py and the parity tests).  /root/reference does not travel to the GPU box; these
 stand-ins are what the GPU tests and bench.py drive, through the same patched methods.
 
-Only the per-frame path is mirrored.  Optimiser surgery, densification and dataset loading are out of scope
- and stay with the reference's own files.
+Beside the per-frame path the classes carry the training surface a loop needs to run on this package alone: `training_setup` (the
+reference's group names, learning rates and `percent_dense`, scene/gaussian_model.py:208-226 and scene/flame_gaussian_model.py:174-207;
+the optimizer is an optim.FusedAdam unless GAA_FUSED_ADAM=0), `update_learning_rate`, `densify_and_prune` (densify.py: include/gdc.h on
+device tensors, its composed-torch statement anywhere else), `prune_points`, `reset_opacity` and `_prune_optimizer` (what spatial_resort
+moves the Adam moments with).  Dataset loading stays with the reference's own files.
 """
 from __future__ import annotations
 
@@ -23,7 +26,51 @@ from torch import nn
 from . import unfused
 
 
-class GaussianModel:
+class _TrainingSetup:
+    """scene/gaussian_model.py:208-234 for the mirror classes: the optimizer of a training run and the position group's schedule.  A base of its
+    own: patch.patch_optimizer wraps the `training_setup` a class itself defines (the reference's), and this one adopts its optimizer itself."""
+
+    def training_setup(self, training_args):
+        """The six splat groups of the reference, by name, with its learning rates; `percent_dense`; fresh densification statistics."""
+        import os
+
+        from . import optim
+
+        n, dev = self._xyz.shape[0], self._xyz.device
+        self.percent_dense = training_args.percent_dense
+        self.xyz_gradient_accum = torch.zeros((n, 1), device=dev)
+        self.denom = torch.zeros((n, 1), device=dev)
+        scale = getattr(self, "spatial_lr_scale", 1.0)
+        groups = [
+            {"params": [self._xyz], "lr": training_args.position_lr_init * scale, "name": "xyz"},
+            {"params": [self._features_dc], "lr": training_args.feature_lr, "name": "f_dc"},
+            {"params": [self._features_rest], "lr": training_args.feature_lr / 20.0, "name": "f_rest"},
+            {"params": [self._opacity], "lr": training_args.opacity_lr, "name": "opacity"},
+            {"params": [self._scaling], "lr": training_args.scaling_lr, "name": "scaling"},
+            {"params": [self._rotation], "lr": training_args.rotation_lr, "name": "rotation"},
+        ]
+        self.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
+        if os.environ.get("GAA_FUSED_ADAM", "1") != "0":
+            self.optimizer = optim.adopt(self.optimizer)
+        self._xyz_lr = (training_args.position_lr_init * scale, training_args.position_lr_final * scale,
+                        getattr(training_args, "position_lr_delay_mult", 1.0), getattr(training_args, "position_lr_max_steps", 1000000))
+
+    def update_learning_rate(self, iteration):
+        """The position group's rate: log-linear from position_lr_init to position_lr_final over position_lr_max_steps (no delay ramp unless
+        position_lr_delay_mult < 1 is combined with delay steps, which the reference never sets)."""
+        lr_init, lr_final, _, max_steps = self._xyz_lr
+        if iteration < 0 or (lr_init == 0.0 and lr_final == 0.0):
+            lr = 0.0
+        else:
+            t = min(max(iteration / max_steps, 0.0), 1.0)
+            lr = float(np.exp(np.log(lr_init) * (1 - t) + np.log(lr_final) * t))
+        for group in self.optimizer.param_groups:
+            if group["name"] == "xyz":
+                group["lr"] = lr
+        return lr
+
+
+class GaussianModel(_TrainingSetup):
     """Accessor surface of the reference GaussianModel (scene/gaussian_model.py:52-163)."""
 
     def __init__(self, sh_degree: int, binding_impl: str = "fused"):
@@ -159,6 +206,30 @@ class GaussianModel:
         if self.active_sh_degree < self.max_sh_degree:
             self.active_sh_degree += 1
 
+    # ---- optimiser surgery and densification (scene/gaussian_model.py:277-280, 349-398, 501-515; training_setup: _TrainingSetup above) ----
+    def _prune_optimizer(self, mask):
+        from . import densify
+
+        return densify.prune_optimizer(self.optimizer, mask)
+
+    def prune_points(self, mask):
+        from . import densify
+
+        densify.prune_points(self, mask)
+
+    def reset_opacity(self):
+        from . import densify
+
+        densify.reset_opacity(self)
+
+    def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size, noise=None):
+        """scene/gaussian_model.py:501-515 through densify.densify_and_prune: five launches and one host read on device tensors."""
+        from . import densify
+
+        densify.densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size, noise=noise)
+
+    densify_and_prune._gaa_fused = True   # patch._hook_spatial_order: already the fused entry, only the re-sort is added
+
 
 class FlameHead(nn.Module):
     """Buffers + forward of the reference FlameHead (flame_model/flame.py:83-184, 485-558) on a rig given
@@ -202,6 +273,19 @@ class FlameGaussianModel(GaussianModel):
             nf = len(self.flame_model.faces)
             self.binding = torch.arange(nf, device=device)
             self.binding_counter = torch.ones(nf, dtype=torch.int32, device=device)
+
+    def training_setup(self, training_args):
+        """scene/flame_gaussian_model.py:174-207: the splat groups plus the pose, translation and expression groups of the FLAME parameters."""
+        super().training_setup(training_args)
+        if self.not_finetune_flame_params:
+            return
+        fp = self.flame_param
+        for k in ("rotation", "neck_pose", "jaw_pose", "eyes_pose", "translation", "expr"):
+            fp[k].requires_grad = True
+        self.optimizer.add_param_group({"params": [fp["rotation"], fp["neck_pose"], fp["jaw_pose"], fp["eyes_pose"]],
+                                        "lr": training_args.flame_pose_lr, "name": "pose"})
+        self.optimizer.add_param_group({"params": [fp["translation"]], "lr": training_args.flame_trans_lr, "name": "trans"})
+        self.optimizer.add_param_group({"params": [fp["expr"]], "lr": training_args.flame_expr_lr, "name": "expr"})
 
     def load_flame_param(self, arrs: Dict[str, np.ndarray], device="cuda", requires_grad: bool = False):
         """flame_param.npz schema (scene/flame_gaussian_model.py:61-71,229-237)."""

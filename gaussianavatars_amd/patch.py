@@ -12,6 +12,7 @@ What is rebound (attribute names, lazy initialisation and autograd connectivity 
     GaussianModel.get_xyz / get_scaling / get_rotation / get_opacity   scene/gaussian_model.py:113-160 -> gab_bind_* (one launch for all four)
     GaussianModel.get_features_split (new)       the two SH leaf tensors, read in place by gsr_forward_ex (no per-frame cat, :152-156)
     gaussian_renderer.render (optional)          gaussian_renderer/__init__.py:19-101   -> the mirror with the split-SH / leaf fast paths
+    GaussianModel.densify_and_prune              scene/gaussian_model.py:501-515        -> gdc_plan + gdc_emit (densify.py; GAA_FUSED_DENSIFY=0 opts out)
 
 `patch_classes` works on any class pair with the reference's attribute names; the repository's own mirror classes
 (gaussianavatars_amd/gaussian_model.py) are written in composed torch like the reference and go through the very same
@@ -248,7 +249,14 @@ def _hook_spatial_order(G) -> None:
         _ORIG[(G, "densify_and_prune")] = dens
 
         def densify_and_prune(self, *a, **k):
-            out = dens(self, *a, **k)
+            # the fused entry (densify.py: include/gdc.h) with the class's own method as what runs outside the kernels' domain; a class whose
+            # method already is that entry (this package's mirror) is called as it is
+            if getattr(dens, "_gaa_fused", False):
+                out = dens(self, *a, **k)
+            else:
+                from . import densify
+
+                out = densify.densify_and_prune(self, *a, fallback=dens, **k)
             from .gaussian_model import spatial_order_default, spatial_resort
 
             if spatial_order_default() and self._xyz.shape[0] > 1:
@@ -368,7 +376,7 @@ def patch_optimizer(gaussian_model_cls, flame_gaussian_model_cls=None) -> list:
     `restore()` goes through `training_setup` (scene/gaussian_model.py:96) and is covered by the same wrap.  Idempotent; undone by
     unpatch_classes; GAA_FUSED_ADAM=0 keeps patch_reference() from calling it.  Returns the names rebound.
 
-    This package's own mirror classes (gaussian_model.py) have no `training_setup`: their users construct `optim.FusedAdam` directly."""
+    This package's own mirror classes (gaussian_model.py) adopt the optimizer inside their own `training_setup`."""
     from . import optim
 
     done = []
