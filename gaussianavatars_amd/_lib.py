@@ -471,7 +471,7 @@ grl_profile_read = partial(profile_read, ("grl",))
 MORE_LIBS = {}
 
 GDC_LIB_PATH = _lib_path("gdc")
-GDC_ABI_VERSION = 1
+GDC_ABI_VERSION = 2
 GDC_CHUNK = 256                # include/gdc.h: splats per workgroup of the scan
 GDC_MAX_TENSORS = 24           # include/gdc.h: tensors one gather launch moves
 GDC_MAX_SPLATS = 1 << 30       # include/gdc.h: P must stay below this
@@ -496,6 +496,9 @@ GDC_SYMBOLS = {
     "gdc_plan": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(GdcParams), _P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, C.POINTER(C.c_int32), _P]),
     "gdc_emit": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(GdcTensor), _P, _P, _P, _P, _P, C.c_int32, _P, _P, _P,
                            _P, _P]),
+    "gdc_order_workspace_bytes": (C.c_int64, [C.c_int32]),
+    "gdc_morton_order": (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    "gdc_permute": (C.c_int, [C.c_int32, _P, C.c_int32, C.POINTER(GdcTensor), _P]),
     **_profile_symbols("gdc"),
 }
 

@@ -8,7 +8,9 @@
 //   k_dc_apply     the scan's third step: every splat's output positions, written as the row map `src`
 //   k_dc_gather    one launch for every tensor: 16 lanes share an output row and move it in 16-byte pieces (a row starts on a 4-byte
 //                  boundary only -- 180 B rows -- so the pieces are typed 4-byte aligned and the compiler picks the widest legal access)
+//   k_dc_permute   the gather's row mover on a plain permutation (gdc_permute): what the spatial re-sort moves a model's rows with
 //
+// The spatial order itself (gdc_morton_order: k_ord_*) is in gdc_order.h.
 // No workgroup waits on another: the scan is three launches, not a look-back.  -ffp-contract=off: the decisions and the children's values
 // round the way gdc.h lists, whatever the compiler would like to fuse.
 #include <hip/hip_runtime.h>
@@ -200,6 +202,19 @@ __global__ __launch_bounds__(BLOCK) void k_dc_apply(int P, const Seg seg, const 
     }
 }
 
+// lane `sub` of the 16 that share a row: rf 4-byte elements from a (or +0.0) to d, in 16-byte pieces and a tail of single elements
+__device__ __forceinline__ void move_row(float* __restrict__ d, const float* __restrict__ a, int rf, int sub, bool zero)
+{
+    const int np = rf >> 2;
+    for (int p = sub; p < np; p += LANES) {
+        f4u v = {0.f, 0.f, 0.f, 0.f};
+        if (!zero) v = *reinterpret_cast<const f4u*>(a + 4 * p);
+        *reinterpret_cast<f4u*>(d + 4 * p) = v;
+    }
+    const int e = (np << 2) + sub;
+    if (e < rf) d[e] = zero ? 0.f : a[e];
+}
+
 __global__ __launch_bounds__(BLOCK) void k_dc_gather(const Table t, int P, const Seg seg, const int* __restrict__ srcmap,
                                                      const float* __restrict__ xyz, const float* __restrict__ scaling,
                                                      const float* __restrict__ rotation, const float* __restrict__ noise,
@@ -218,16 +233,7 @@ __global__ __launch_bounds__(BLOCK) void k_dc_gather(const Table t, int P, const
         const int rf = t.row_floats[k], kind = t.kind[k];
         if (child && (kind == GDC_XYZ || kind == GDC_SCALING)) continue;   // written below
         const bool zero = kind == GDC_ZERO || (kind == GDC_MOMENT && born);
-        float* __restrict__ d = t.dst[k] + (size_t)row * rf;
-        const float* __restrict__ a = zero ? nullptr : t.src[k] + (size_t)source * rf;
-        const int np = rf >> 2;
-        for (int p = sub; p < np; p += LANES) {
-            f4u v = {0.f, 0.f, 0.f, 0.f};
-            if (!zero) v = *reinterpret_cast<const f4u*>(a + 4 * p);
-            *reinterpret_cast<f4u*>(d + 4 * p) = v;
-        }
-        const int e = (np << 2) + sub;
-        if (e < rf) d[e] = zero ? 0.f : a[e];
+        move_row(t.dst[k] + (size_t)row * rf, zero ? nullptr : t.src[k] + (size_t)source * rf, rf, sub, zero);
     }
     if (binding && sub == 1) {
         if (is64) reinterpret_cast<long long*>(binding_out)[row] = reinterpret_cast<const long long*>(binding)[source];
@@ -257,6 +263,20 @@ __global__ __launch_bounds__(BLOCK) void k_dc_gather(const Table t, int P, const
     }
 }
 
+// gdc_permute: dst[r] = src[perm[r]] for every tensor of the table, on the gather's row mover; an index outside [0, P) reads nothing: +0.0
+__global__ __launch_bounds__(BLOCK) void k_dc_permute(const Table t, int P, const int* __restrict__ perm)
+{
+    const int tid = (int)threadIdx.x, sub = tid & (LANES - 1);
+    const int row = (int)(blockIdx.x * GDC_ROWS) + (tid >> 4);
+    if (row >= P) return;
+    const int source = perm[row];
+    const bool zero = (unsigned)source >= (unsigned)P;
+    for (int k = 0; k < t.n; ++k) {
+        const int rf = t.row_floats[k];
+        move_row(t.dst[k] + (size_t)row * rf, zero ? nullptr : t.src[k] + (size_t)source * rf, rf, sub, zero);
+    }
+}
+
 // the workspace, in 4-byte units: totals[4] | cnt[F] | cand[F] | sums[4 * nchunks] | code[P bytes]
 struct Workspace { int* totals; int* cnt; int* cand; int* sums; unsigned char* code; int nchunks; };
 
@@ -273,6 +293,8 @@ static Workspace carve(void* base, int P, int F)
 }
 
 }  // namespace gdc
+
+#include "gdc_order.h"
 
 #define HIP_CHECK(call, what)                                                                 \
     do {                                                                                      \
@@ -391,6 +413,75 @@ int gdc_emit(int32_t P, int32_t F, const int32_t* totals, int32_t ntensors, cons
                 (const int*)src_out, (const float*)xyz, (const float*)scaling, (const float*)rotation, (const float*)noise, binding,
                 (int)binding_is_i64, (const float*)face_scaling, xyz_out, scaling_out, binding_out);
     LAUNCH_CHECK(GDC_E_HIP, "k_dc_gather");
+    return GDC_OK;
+}
+
+int64_t gdc_order_workspace_bytes(int32_t P)
+{
+    if (P < 0 || P >= GDC_MAX_SPLATS) return -1;
+    const int64_t nchunks = ((int64_t)P + gdc::BLOCK - 1) / gdc::BLOCK;
+    return 4 * (gdc::ORD_HEAD + 4 * (int64_t)P + gdc::RADIX * nchunks);
+}
+
+int gdc_morton_order(int32_t P, int32_t F, const void* xyz, const void* binding, int32_t binding_is_i64, const void* face_centers,
+                     void* perm_out, void* workspace, void* stream_)
+{
+    if (P < 0 || P >= GDC_MAX_SPLATS || F < 0) return fail(GDC_E_ARG, "bad arguments: P = %d outside [0, %d) or F = %d < 0", (int)P, GDC_MAX_SPLATS, (int)F);
+    if ((binding != nullptr) != (face_centers != nullptr) || (binding && F <= 0))
+        return fail(GDC_E_ARG, "bad arguments: a bound model needs binding, face_centers and F > 0; an unbound one neither pointer");
+    if (P == 0) return GDC_OK;
+    if (!xyz || !perm_out || !workspace) return fail(GDC_E_ARG, "bad arguments: NULL pointer");
+    if (misaligned(xyz) || misaligned(perm_out) || misaligned(workspace) || misaligned(face_centers) || (((uintptr_t)binding) & (binding_is_i64 ? 7 : 3)))
+        return fail(GDC_E_ARG, "bad arguments: pointers must be aligned to their element");
+    hipStream_t stream = (hipStream_t)stream_;
+    const gdc::OrderWorkspace w = gdc::carve_order(workspace, P);
+    const dim3 grid((unsigned)w.nchunks), block(gdc::BLOCK);
+    PROF_LAUNCH(gdc::k_ord_clear, dim3((gdc::ORD_HEAD + gdc::BLOCK - 1) / gdc::BLOCK), block, 0, stream, (int*)w.box);
+    LAUNCH_CHECK(GDC_E_HIP, "k_ord_clear");
+    PROF_LAUNCH(gdc::k_ord_bounds, grid, block, 0, stream, (int)P, (int)F, (const float*)xyz, binding, (int)binding_is_i64,
+                (const float*)face_centers, w.box);
+    LAUNCH_CHECK(GDC_E_HIP, "k_ord_bounds");
+    PROF_LAUNCH(gdc::k_ord_codes, grid, block, 0, stream, (int)P, (int)F, (const float*)xyz, binding, (int)binding_is_i64,
+                (const float*)face_centers, (const unsigned*)w.box, w.keys[0]);
+    LAUNCH_CHECK(GDC_E_HIP, "k_ord_codes");
+    for (int pass = 0; pass < gdc::PASSES; ++pass) {   // keys ping-pong between the two buffers; the last pass writes the rows to perm_out
+        const int shift = pass * gdc::RADIX_BITS, in = pass & 1, out = in ^ 1;
+        const bool last = pass == gdc::PASSES - 1;
+        int* totals = w.totals + pass * gdc::RADIX;
+        PROF_LAUNCH(gdc::k_ord_hist, grid, block, 0, stream, (int)P, w.nchunks, shift, (const unsigned*)w.keys[in], w.table, totals);
+        LAUNCH_CHECK(GDC_E_HIP, "k_ord_hist");
+        PROF_LAUNCH(gdc::k_ord_scan, dim3(gdc::RADIX), block, 0, stream, w.nchunks, w.table, (const int*)totals);
+        LAUNCH_CHECK(GDC_E_HIP, "k_ord_scan");
+        PROF_LAUNCH(gdc::k_ord_scatter, grid, block, 0, stream, (int)P, w.nchunks, shift, (const unsigned*)w.keys[in],
+                    (const int*)(pass == 0 ? nullptr : w.vals[in]), (const int*)w.table, last ? (unsigned*)nullptr : w.keys[out],
+                    last ? (int*)perm_out : w.vals[out]);
+        LAUNCH_CHECK(GDC_E_HIP, "k_ord_scatter");
+    }
+    return GDC_OK;
+}
+
+int gdc_permute(int32_t P, const void* perm, int32_t ntensors, const GdcTensor* tensors, void* stream_)
+{
+    if (P < 0 || P >= GDC_MAX_SPLATS) return fail(GDC_E_ARG, "bad arguments: P = %d outside [0, %d)", (int)P, GDC_MAX_SPLATS);
+    if (ntensors < 0 || ntensors > GDC_MAX_TENSORS || (ntensors > 0 && !tensors))
+        return fail(GDC_E_ARG, "bad arguments: ntensors outside [0, %d] or NULL table", GDC_MAX_TENSORS);
+    if (P == 0 || ntensors == 0) return GDC_OK;
+    if (!perm) return fail(GDC_E_ARG, "bad arguments: NULL pointer");
+    if (misaligned(perm)) return fail(GDC_E_ARG, "bad arguments: pointers must be aligned to their element");
+    gdc::Table t;
+    for (int k = 0; k < gdc::T; ++k) {
+        t.src[k] = nullptr, t.dst[k] = nullptr, t.row_floats[k] = 0, t.kind[k] = GDC_COPY;
+        if (k >= ntensors) continue;
+        const GdcTensor& a = tensors[k];
+        if (a.row_floats < 0 || a.kind != GDC_COPY) return fail(GDC_E_ARG, "tensor %d: bad row_floats, or a kind other than GDC_COPY", k);
+        if (a.row_floats > 0 && (!a.dst || !a.src)) return fail(GDC_E_ARG, "tensor %d: NULL pointer", k);
+        if (misaligned(a.src) || misaligned(a.dst)) return fail(GDC_E_ARG, "tensor %d: pointers must be 4-byte aligned", k);
+        t.src[k] = (const float*)a.src, t.dst[k] = (float*)a.dst, t.row_floats[k] = a.row_floats;
+    }
+    t.n = ntensors;
+    PROF_LAUNCH(gdc::k_dc_permute, dim3((unsigned)(((int64_t)P + GDC_ROWS - 1) / GDC_ROWS)), dim3(gdc::BLOCK), 0, (hipStream_t)stream_, t, (int)P,
+                (const int*)perm);
+    LAUNCH_CHECK(GDC_E_HIP, "k_dc_permute");
     return GDC_OK;
 }
 

@@ -11,6 +11,9 @@ counts read back) as five launches and ONE host read.
         mirror classes, the A/B leg of tools/densify_timing.py and the error bar of tests/test_densify_gpu.py)
     prune_points / reset_opacity / prune_optimizer / replace_tensor
         the remaining optimiser surgery of the training loop, composed torch, for classes that do not bring their own
+    morton_permutation / permute_rows
+        the spatial re-sort that follows a densification (gaussian_model.spatial_resort), on bare device tensors: io.morton_order's permutation
+        bit for bit, and every per-splat tensor moved by it in one launch -- nothing is copied to the host and nothing synchronises
 
 `noise` (2, P, 3) are the unit normals of the split's children, child c of splat i from noise[c, i].  None draws torch.randn(2, P, 3) on the
 device: the same distribution as the reference's torch.normal(mean=0, std=scaling), NOT the same stream -- a seeded reference run and a seeded
@@ -32,7 +35,7 @@ from torch import nn
 from . import _lib
 
 __all__ = ["densify_and_prune", "density_control_fused", "density_control_composed", "prune_points", "reset_opacity", "prune_optimizer",
-           "replace_tensor", "SPLAT_GROUPS"]
+           "replace_tensor", "morton_permutation", "permute_rows", "SPLAT_GROUPS"]
 
 #: optimizer group name -> leaf attribute (scene/gaussian_model.py:213-220)
 SPLAT_GROUPS = {"xyz": "_xyz", "f_dc": "_features_dc", "f_rest": "_features_rest", "opacity": "_opacity", "scaling": "_scaling",
@@ -196,6 +199,98 @@ def density_control_composed(leaves, moments, accum, denom, noise, max_grad, min
             "denom": torch.zeros((N, 1), device=dev), "max_radii2D": torch.zeros((N,), device=dev),
             "binding": binding[source] if bound else None, "binding_counter": counter,
             "totals": (n0, seg[1].shape[0], n2, n2)}
+
+
+# ------------------------------------------------------------------------------------------------
+# the spatial order on bare tensors (include/gdc.h, ABI 2)
+# ------------------------------------------------------------------------------------------------
+_ORDER_WS = {}   # (device index, raw stream) -> gdc_morton_order's scratch; never shared between two streams
+
+
+def _order_workspace(dev, stream, nbytes):
+    """The (device, stream)'s scratch, grown when a larger model arrives; the library clears what it needs on every call.  Under stream
+    capture nothing is cached: a scratch made there lives in that graph's private pool."""
+    key = (dev.index, stream)
+    held = _ORDER_WS.get(key)
+    if held is not None and held.numel() * 4 >= nbytes:
+        return held
+    held = torch.empty(max(nbytes // 4, 1024), dtype=torch.int32, device=dev)
+    if not torch.cuda.is_current_stream_capturing():
+        _ORDER_WS[key] = held
+    return held
+
+
+def _morton_i32(xyz, binding, face_centers):
+    """morton_permutation as the int32 tensor the library writes."""
+    if not isinstance(xyz, torch.Tensor) or xyz.device.type != "cuda":
+        raise RuntimeError("morton_permutation needs device tensors: the host statement is io.morton_order")
+    dev = xyz.device
+    xyz = xyz.detach()
+    if not _dense(xyz, dev) or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError("xyz must be a contiguous fp32 tensor of shape (P, 3)")
+    P, F, is64 = xyz.shape[0], 0, 0
+    if (binding is None) != (face_centers is None):
+        raise ValueError("binding and face_centers are given together (a bound model) or not at all")
+    if binding is not None:
+        if binding.dtype not in (torch.int32, torch.int64) or not _dense(binding, dev, binding.dtype) or binding.shape != (P,):
+            raise ValueError("binding must be a contiguous int32 / int64 tensor of P elements")
+        if not _dense(face_centers, dev) or face_centers.dim() != 2 or face_centers.shape[1] != 3 or face_centers.shape[0] < 1:
+            raise ValueError("face_centers must be a contiguous fp32 tensor of shape (F, 3), F > 0")
+        F, is64 = face_centers.shape[0], 1 if binding.dtype is torch.int64 else 0
+    lib = _lib.gdc()
+    nbytes = lib.gdc_order_workspace_bytes(P)
+    if nbytes < 0:
+        raise ValueError(f"P = {P} is outside [0, {_lib.GDC_MAX_SPLATS})")
+    with _lib.on_device(dev):
+        stream = _lib.raw_stream(dev)
+        perm = torch.empty(P, dtype=torch.int32, device=dev)
+        ws = _order_workspace(dev, stream, nbytes)
+        if lib.gdc_morton_order(P, F, xyz.data_ptr(), None if binding is None else binding.data_ptr(), is64,
+                                None if face_centers is None else face_centers.data_ptr(), perm.data_ptr(), ws.data_ptr(), stream) != 0:
+            raise RuntimeError(f"gdc_morton_order failed: {_lib.gdc_error()}")
+    return perm
+
+
+@torch.no_grad()
+def morton_permutation(xyz, binding=None, face_centers=None, dtype=torch.int64):
+    """io.morton_order of the positions the splats are ordered by, as a device tensor, bit for bit: `xyz` (P, 3) fp32 for an unbound model,
+    `face_centers[binding] + 1e-3 * xyz` in fp32 for a bound one (face_centers (F, 3) fp32, binding int32 / int64).  The library's fifteen
+    launches on the current stream; no host read, no synchronisation, so the call can be recorded into a graph.  `dtype`: torch.int64 (what
+    indexing wants: one more element-wise kernel) or torch.int32, the tensor the library wrote, which permute_rows takes as it is."""
+    if dtype not in (torch.int32, torch.int64):
+        raise ValueError("dtype must be torch.int32 or torch.int64")
+    perm = _morton_i32(xyz, binding, face_centers)
+    return perm if dtype is torch.int32 else perm.long()
+
+
+@torch.no_grad()
+def permute_rows(tensors, perm):
+    """[t[perm] for t in tensors] as new tensors, in ONE launch (one more for every further GDC_MAX_TENSORS tensors): contiguous device
+    tensors of P rows and 4- or 8-byte elements (an int64 row moves as two 4-byte elements per entry), perm (P,) int32 -- used as it is --
+    or int64, which costs one conversion kernel first."""
+    tensors = [t.detach() for t in tensors]
+    if not isinstance(perm, torch.Tensor) or perm.device.type != "cuda" or perm.dtype not in (torch.int32, torch.int64) or perm.dim() != 1:
+        raise ValueError("perm must be an int32 / int64 device vector")
+    dev, P = perm.device, perm.shape[0]
+    perm = perm.to(torch.int32).contiguous()
+    rows = []
+    for k, t in enumerate(tensors):
+        if not _dense(t, dev, t.dtype) or t.dim() < 1 or t.shape[0] != P or t.element_size() not in (4, 8):
+            raise ValueError(f"tensor {k} must be a contiguous tensor of {P} rows of 4- or 8-byte elements on {dev}")
+        rows.append(_row_floats(t) * (t.element_size() // 4))
+    if P >= _lib.GDC_MAX_SPLATS:
+        raise ValueError(f"P = {P} is outside [0, {_lib.GDC_MAX_SPLATS})")
+    lib = _lib.gdc()
+    out = [torch.empty_like(t) for t in tensors]
+    with _lib.on_device(dev):
+        stream = _lib.raw_stream(dev)
+        for at in range(0, len(tensors), _lib.GDC_MAX_TENSORS):
+            part = [(t.data_ptr(), o.data_ptr(), rf, _lib.GDC_COPY) for t, o, rf in
+                    zip(tensors[at:at + _lib.GDC_MAX_TENSORS], out[at:at + _lib.GDC_MAX_TENSORS], rows[at:at + _lib.GDC_MAX_TENSORS])]
+            table = (_lib.GdcTensor * len(part))(*part)
+            if lib.gdc_permute(P, perm.data_ptr(), len(part), table, stream) != 0:
+                raise RuntimeError(f"gdc_permute failed: {_lib.gdc_error()}")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

@@ -373,13 +373,135 @@ def template_face_centers(model):
     return v[f].mean(1)
 
 
-def spatial_resort(model) -> torch.Tensor:
+def _device_face_centers(model, dev):
+    """template_face_centers as an (F, 3) fp32 tensor on `dev`, built and uploaded once per template and kept with the model; None for a model
+    without a mesh, or whose template is not fp32 (the host statement then computes the positions in another precision)."""
+    fm = getattr(model, "flame_model", None)
+    if fm is None or not hasattr(fm, "v_template") or not hasattr(fm, "faces"):
+        return None
+    key = (fm.v_template.data_ptr(), fm.v_template._version, fm.faces.data_ptr(), fm.faces._version, str(dev))
+    held = getattr(model, "_gaa_face_centers", None)
+    if held is None or held[0] != key:
+        centers = template_face_centers(model)
+        held = (key, torch.from_numpy(np.ascontiguousarray(centers)).to(dev) if centers.dtype == np.float32 else None)
+        model._gaa_face_centers = held
+    return held[1]
+
+
+def _spatial_resort_fused(model):
+    """spatial_resort on the kernels of include/gdc.h (ABI 2) when the model is inside their domain, else None: one densify.morton_permutation
+    and one densify.permute_rows over the six leaves, the moments the optimizer holds for them, the three statistics, `binding` and a tracked
+    `_gaa_order` (23 tensors at most), installed the way densify._install and densify.prune_optimizer do.  Nothing is copied to the host and
+    nothing synchronises."""
+    import os
+
+    from . import _lib, densify
+
+    if os.environ.get("GAA_FUSED_RESORT", "1") == "0":
+        return None
+    xyz = getattr(model, "_xyz", None)
+    if not isinstance(xyz, torch.Tensor) or xyz.device.type != "cuda" or xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] >= _lib.GDC_MAX_SPLATS:
+        return None
+    dev, P = xyz.device, xyz.shape[0]
+    if torch.cuda.is_current_stream_capturing():
+        return None
+    attrs = tuple(densify.SPLAT_GROUPS.values())
+    if not all(densify._dense(getattr(model, a, None), dev) and getattr(model, a).shape[0] == P for a in attrs):
+        return None
+    binding = getattr(model, "binding", None)
+    centers = None
+    if binding is not None:
+        if not isinstance(binding, torch.Tensor) or binding.dtype not in (torch.int32, torch.int64) or not densify._dense(binding, dev, binding.dtype) \
+                or binding.shape != (P,):
+            return None
+        fm = getattr(model, "flame_model", None)
+        if fm is not None and hasattr(fm, "v_template") and hasattr(fm, "faces"):
+            centers = _device_face_centers(model, dev)
+            if centers is None:
+                return None
+    optimizer = getattr(model, "optimizer", None)
+    groups = None
+    if optimizer is not None:
+        groups = densify._splat_groups(optimizer)
+        if groups is None or any(g["params"][0] is not getattr(model, a) for a, g in groups.items()):
+            return None
+    names, tensors = [], []
+    for a in attrs:
+        names.append(a)
+        tensors.append(getattr(model, a).detach())
+        state = optimizer.state.get(getattr(model, a)) if groups is not None else None
+        if state:
+            # Adam's two moments and nothing else per row: any other state (another optimizer's buffers, amsgrad's maximum) is the host path's
+            if "exp_avg" not in state or "exp_avg_sq" not in state:
+                return None
+            if any(isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == P for k, v in state.items() if k not in ("exp_avg", "exp_avg_sq")):
+                return None
+            for key in ("exp_avg", "exp_avg_sq"):
+                if not densify._dense(state[key], dev) or state[key].shape != getattr(model, a).shape:
+                    return None
+                names.append((a, key))
+                tensors.append(state[key])
+    for aux in ("xyz_gradient_accum", "denom", "max_radii2D"):
+        t = getattr(model, aux, None)
+        if isinstance(t, torch.Tensor) and t.dim() >= 1 and t.shape[0] == P:
+            if not densify._dense(t, dev):
+                return None
+            names.append(aux)
+            tensors.append(t)
+    if binding is not None:
+        names.append("binding")
+        tensors.append(binding)
+    prev = getattr(model, "_gaa_order", None)
+    tracked = isinstance(prev, torch.Tensor) and prev.shape[0] == P
+    if tracked:
+        if prev.dtype not in (torch.int32, torch.int64) or prev.dim() != 1:
+            return None
+        names.append("_gaa_order")
+        tensors.append(prev.to(dev).contiguous())
+    with torch.no_grad():
+        perm32 = densify._morton_i32(xyz, binding if centers is not None else None, centers)
+        moved = dict(zip(names, densify.permute_rows(tensors, perm32)))
+        perm = perm32.long()
+        for a in attrs:
+            old = getattr(model, a)
+            p = nn.Parameter(moved[a], requires_grad=old.requires_grad)
+            if groups is not None:
+                state = optimizer.state.get(old)
+                if state is not None:
+                    del optimizer.state[old]
+                    if (a, "exp_avg") in moved:
+                        state["exp_avg"], state["exp_avg_sq"] = moved[(a, "exp_avg")], moved[(a, "exp_avg_sq")]
+                    optimizer.state[p] = state
+                groups[a]["params"][0] = p
+            setattr(model, a, p)
+        for aux in ("xyz_gradient_accum", "denom", "max_radii2D", "binding"):
+            if aux in moved:
+                setattr(model, aux, moved[aux])
+        if tracked:
+            model._gaa_order = moved["_gaa_order"]
+        elif prev is None and not getattr(model, "_gaa_order_lost", False):
+            model._gaa_order = perm.clone()
+        else:
+            model._gaa_order = None
+            model._gaa_order_lost = True
+    return perm
+
+
+def spatial_resort(model, fused: Optional[bool] = None) -> torch.Tensor:
     """Puts the splats of a LIVE model -- this package's classes or the reference's own -- into Morton order of their positions
     (io.spatial_sort) and returns the permutation.  Densification appends its new splats (scene/gaussian_model.py:426-515), so a model that
     was loaded in order drifts out of it; this is the re-sort.  Everything that is indexed by splat moves together: the six leaf
     parameters, with an optimiser attached their Adam moments too -- through the reference's own `_prune_optimizer` (:349-371), which indexes
     parameters and moments with whatever it is given: a permutation instead of a keep-mask --, the densification statistics
-    (xyz_gradient_accum, denom, max_radii2D) and the binding.  Recorded steps (graphs.py) must be captured again afterwards."""
+    (xyz_gradient_accum, denom, max_radii2D) and the binding.  Recorded steps (graphs.py) must be captured again afterwards.
+
+    A model of contiguous fp32 device tensors (binding / `_gaa_order` integer) takes the kernels of include/gdc.h instead -- the same
+    permutation and the same rows, bit for bit, without a copy to the host or a synchronisation (_spatial_resort_fused; DESIGN.md section 14);
+    GAA_FUSED_RESORT=0 or `fused=False` keep the host statement below, which is also what runs anywhere outside that domain."""
+    if fused is None or fused:
+        perm = _spatial_resort_fused(model)
+        if perm is not None:
+            return perm
     from . import io as gio
 
     with torch.no_grad():

@@ -188,9 +188,9 @@ def _hook_spatial_order(G) -> None:
     GAA_SPATIAL_SORT=0 opts out): after `load_ply` (scene/gaussian_model.py:282-332; the reference's FlameGaussianModel.load_ply calls it
     through super()) and after every `densify_and_prune` (:501-515, called from train.py:197-206), which appends its new splats at the end.
     The order is a layout choice -- images and gradients do not depend on it -- that lets a workgroup of the binning pass meet a compact set
-    of tiles.  gaussian_model.spatial_resort moves the six leaves, their Adam moments (through the model's own
-    _prune_optimizer), the densification statistics and the binding together.  Classes whose load_ply takes `spatial_sort` itself (this
-    package's mirror) are left alone."""
+    of tiles.  gaussian_model.spatial_resort moves the six leaves, their Adam moments, the densification statistics and
+    the binding together: on the device for a model of fp32 device tensors (include/gdc.h ABI 2), through the model's
+    own _prune_optimizer anywhere else.  Classes whose load_ply takes `spatial_sort` itself (this package's mirror) are left alone."""
     import inspect
 
     load = G.__dict__.get("load_ply")
@@ -260,7 +260,10 @@ def _hook_spatial_order(G) -> None:
             from .gaussian_model import spatial_order_default, spatial_resort
 
             if spatial_order_default() and self._xyz.shape[0] > 1:
-                spatial_resort(self)
+                # a reference class takes spatial_resort's device path (include/gdc.h, ABI 2) where it applies; the mirror's own entry keeps the
+                # host statement: its densify_and_prune is pinned to the five gdc launches of the density control itself
+                # (tests/test_densify_gpu.py counts them with the order hook on)
+                spatial_resort(self, fused=False if getattr(dens, "_gaa_fused", False) else None)
             return out
 
         densify_and_prune.__doc__ = dens.__doc__

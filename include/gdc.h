@@ -2,7 +2,7 @@
  * gdc.h -- C ABI of adaptive density control ("Gaussian density control"): the end state of the reference's
  * `densify_and_prune` (scene/gaussian_model.py:501-515: densify_and_clone, densify_and_split, prune_points) in five launches
  * and ONE host read, for the six leaves, their twelve Adam moments, the three statistics, `binding` and `binding_counter`.
- * tests/densify_ref.py states the same contract in float64 numpy.
+ * tests/densify_ref.py states the same contract in float64 numpy.  Since ABI 2 also the spatial re-sort that follows it (last block below).
  *
  * Conventions as gop.h: DEVICE pointers, fp32 / int32, contiguous, 4-byte aligned; 0 / <0 return codes with gdc_last_error();
  * everything is enqueued on `stream`.  gdc_plan() ends with the only host synchronisation of a call: it waits for the 16-byte
@@ -33,6 +33,24 @@
  *     src[r]  the source row of a surviving original, -1 - source of a new row
  *     leaves  gathered / computed as above;  moments: gathered for originals, +0.0 for new rows;  the three statistics: +0.0
  *     binding[r] = binding[source];  binding_counter[f] = cnt[f] - (removed ? cand[f] : 0)  (== bincount(binding) when it was on entry)
+ *
+ * The spatial order (ABI 2): gdc_morton_order() is io.morton_order's permutation of the splats along the Z-order curve of their bounding
+ * box, bit for bit, and gdc_permute() moves every per-splat tensor by it in one launch.  Nothing is read back, nothing synchronises and
+ * nothing is allocated: both calls can be recorded into a graph.
+ *     position   unbound: p = xyz[i].  Bound: p = centre[binding[i]] + 1e-3f * xyz[i] in fp32 -- one rounded multiply, one rounded add, no
+ *                contraction -- with centre the (F, 3) fp32 table of the template's face centres; a binding outside [0, F) reads nothing
+ *                and uses the centre (0, 0, 0) (an int64 binding is compared as 64 bits here)
+ *     box        lo, hi = per-axis min / max of p over the splats: exact, so the order of the reduction does not matter (integer
+ *                atomics on an order-preserving encoding of the floats; no float atomics)
+ *     quantise   in fp64, in numpy's order: q = clip(trunc(((double)p - lo) / max((double)hi - lo, 1e-30) * 1023.0), 0, 1023), clamped
+ *                before the conversion to an integer
+ *     code       bit b (0..9) of axis a (0..2) goes to bit 3 b + a
+ *     order      ascending code, ties by row index: perm[r] = the row that comes r-th, a stable LSD radix sort of (code, row) in four
+ *                8-bit passes of histogram, scan and scatter (three launches each; no workgroup waits on another); a scatter ranks the
+ *                keys of its 256-key chunk by a ballot match per digit bit, lanes and waves in order, so every pass is stable and the
+ *                result does not depend on scheduling
+ *     non-finite positions are outside the contract (numpy's answer is undefined); perm is still a permutation of 0..P-1, the same on
+ *                every call, and nothing is stored out of range
  */
 #ifndef GDC_H
 #define GDC_H
@@ -44,7 +62,7 @@
 extern "C" {
 #endif
 
-#define GDC_ABI_VERSION 1
+#define GDC_ABI_VERSION 2
 #define GDC_OK 0
 #define GDC_E_ARG (-1)
 #define GDC_E_HIP (-2)
@@ -99,6 +117,21 @@ int gdc_plan(int32_t P, int32_t F, const GdcParams* params, const void* scaling,
 int gdc_emit(int32_t P, int32_t F, const int32_t* totals, int32_t ntensors, const GdcTensor* tensors, const void* xyz, const void* scaling,
              const void* rotation, const void* noise, const void* binding, int32_t binding_is_i64, const void* face_scaling,
              void* src_out, void* binding_out, void* workspace, void* stream);
+
+/* bytes of gdc_morton_order's scratch buffer (4-byte aligned; its contents need not survive between calls): the box and the digit totals,
+ * two key and two row buffers of P words and the RADIX x chunks table.  Monotonic in P; -1 when P is outside [0, GDC_MAX_SPLATS). */
+int64_t gdc_order_workspace_bytes(int32_t P);
+
+/* perm_out (P, int32) = the spatial order of the text above: 3 + 4 x 3 launches (kernels only).  xyz (P, 3) fp32; binding (P, int32 or
+ * int64) and face_centers (F, 3) fp32 are given together (bound, F > 0) or both NULL (unbound).  P == 0 launches nothing; P == 1 gives {0}. */
+int gdc_morton_order(int32_t P, int32_t F, const void* xyz, const void* binding, int32_t binding_is_i64, const void* face_centers,
+                     void* perm_out, void* workspace, void* stream);
+
+/* dst[r] = src[perm[r]], r < P, for every tensor of the HOST table (ntensors <= GDC_MAX_TENSORS, every kind GDC_COPY, dst and src distinct
+ * buffers of P rows) in ONE launch of the gather's row mover: 16 lanes per row, 16-byte pieces typed for 4-byte alignment.  An int64 tensor is
+ * a row of two 4-byte elements; row_floats == 0 moves nothing; perm[r] outside [0, P) reads nothing and writes +0.0.  P == 0 or
+ * ntensors == 0 launches nothing. */
+int gdc_permute(int32_t P, const void* perm, int32_t ntensors, const GdcTensor* tensors, void* stream);
 
 /* Optional per-kernel timing, as gop_profile_* (include/gop.h). */
 int gdc_profile_enable(int on);
