@@ -464,7 +464,7 @@ grl_profile_read = partial(profile_read, ("grl",))
 
 
 # ------------------------------------------------------------------------------------------------
-# libgdc_hip.so : adaptive density control (include/gdc.h).  Loaded only by densify.py, at the first densification on device tensors.
+# libgdc_hip.so : adaptive density control (include/gdc.h).  Loaded only by densify.py and knn.py, at the first call on device tensors.
 # ------------------------------------------------------------------------------------------------
 #: tag -> LibSpec of the libraries added after LIBS was pinned to its six tags (tests/test_lib_loader_cpu.py); handle(), last_error() and the
 #: profile shims take these tags exactly like those of LIBS, and build() checks both tables
@@ -475,6 +475,7 @@ GDC_ABI_VERSION = 2
 GDC_CHUNK = 256                # include/gdc.h: splats per workgroup of the scan
 GDC_MAX_TENSORS = 24           # include/gdc.h: tensors one gather launch moves
 GDC_MAX_SPLATS = 1 << 30       # include/gdc.h: P must stay below this
+GDC_KNN_CHUNK = 32             # include/gdc.h: sorted points per box of the nearest-neighbour search
 GDC_COPY, GDC_MOMENT, GDC_ZERO, GDC_XYZ, GDC_SCALING = range(5)   # include/gdc.h: GdcTensor.kind
 
 
@@ -499,6 +500,8 @@ GDC_SYMBOLS = {
     "gdc_order_workspace_bytes": (C.c_int64, [C.c_int32]),
     "gdc_morton_order": (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P]),
     "gdc_permute": (C.c_int, [C.c_int32, _P, C.c_int32, C.POINTER(GdcTensor), _P]),
+    "gdc_knn_workspace_bytes": (C.c_int64, [C.c_int32]),
+    "gdc_knn3_dist2": (C.c_int, [C.c_int32, _P, _P, _P, _P]),
     **_profile_symbols("gdc"),
 }
 

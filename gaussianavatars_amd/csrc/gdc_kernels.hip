@@ -10,7 +10,7 @@
 //                  boundary only -- 180 B rows -- so the pieces are typed 4-byte aligned and the compiler picks the widest legal access)
 //   k_dc_permute   the gather's row mover on a plain permutation (gdc_permute): what the spatial re-sort moves a model's rows with
 //
-// The spatial order itself (gdc_morton_order: k_ord_*) is in gdc_order.h.
+// The spatial order itself (gdc_morton_order: k_ord_*) is in gdc_order.h, the nearest-neighbour search on it (gdc_knn3_dist2: k_knn_*) in gdc_knn.h.
 // No workgroup waits on another: the scan is three launches, not a look-back.  -ffp-contract=off: the decisions and the children's values
 // round the way gdc.h lists, whatever the compiler would like to fuse.
 #include <hip/hip_runtime.h>
@@ -295,12 +295,43 @@ static Workspace carve(void* base, int P, int F)
 }  // namespace gdc
 
 #include "gdc_order.h"
+#include "gdc_knn.h"
 
 #define HIP_CHECK(call, what)                                                                 \
     do {                                                                                      \
         hipError_t e_ = (call);                                                               \
         if (e_ != hipSuccess) return fail(GDC_E_HIP, "%s: %s", what, hipGetErrorString(e_));  \
     } while (0)
+
+// the fifteen launches of the spatial order (gdc_morton_order, and the first step of gdc_knn3_dist2): arguments already checked
+static int enqueue_order(int P, int F, const void* xyz, const void* binding, int is64, const void* face_centers, void* perm_out, void* workspace,
+                         hipStream_t stream)
+{
+    const gdc::OrderWorkspace w = gdc::carve_order(workspace, P);
+    const dim3 grid((unsigned)w.nchunks), block(gdc::BLOCK);
+    PROF_LAUNCH(gdc::k_ord_clear, dim3((gdc::ORD_HEAD + gdc::BLOCK - 1) / gdc::BLOCK), block, 0, stream, (int*)w.box);
+    LAUNCH_CHECK(GDC_E_HIP, "k_ord_clear");
+    PROF_LAUNCH(gdc::k_ord_bounds, grid, block, 0, stream, (int)P, (int)F, (const float*)xyz, binding, is64,
+                (const float*)face_centers, w.box);
+    LAUNCH_CHECK(GDC_E_HIP, "k_ord_bounds");
+    PROF_LAUNCH(gdc::k_ord_codes, grid, block, 0, stream, (int)P, (int)F, (const float*)xyz, binding, is64,
+                (const float*)face_centers, (const unsigned*)w.box, w.keys[0]);
+    LAUNCH_CHECK(GDC_E_HIP, "k_ord_codes");
+    for (int pass = 0; pass < gdc::PASSES; ++pass) {   // keys ping-pong between the two buffers; the last pass writes the rows to perm_out
+        const int shift = pass * gdc::RADIX_BITS, in = pass & 1, out = in ^ 1;
+        const bool last = pass == gdc::PASSES - 1;
+        int* totals = w.totals + pass * gdc::RADIX;
+        PROF_LAUNCH(gdc::k_ord_hist, grid, block, 0, stream, (int)P, w.nchunks, shift, (const unsigned*)w.keys[in], w.table, totals);
+        LAUNCH_CHECK(GDC_E_HIP, "k_ord_hist");
+        PROF_LAUNCH(gdc::k_ord_scan, dim3(gdc::RADIX), block, 0, stream, w.nchunks, w.table, (const int*)totals);
+        LAUNCH_CHECK(GDC_E_HIP, "k_ord_scan");
+        PROF_LAUNCH(gdc::k_ord_scatter, grid, block, 0, stream, (int)P, w.nchunks, shift, (const unsigned*)w.keys[in],
+                    (const int*)(pass == 0 ? nullptr : w.vals[in]), (const int*)w.table, last ? (unsigned*)nullptr : w.keys[out],
+                    last ? (int*)perm_out : w.vals[out]);
+        LAUNCH_CHECK(GDC_E_HIP, "k_ord_scatter");
+    }
+    return GDC_OK;
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 extern "C" {
@@ -433,31 +464,7 @@ int gdc_morton_order(int32_t P, int32_t F, const void* xyz, const void* binding,
     if (!xyz || !perm_out || !workspace) return fail(GDC_E_ARG, "bad arguments: NULL pointer");
     if (misaligned(xyz) || misaligned(perm_out) || misaligned(workspace) || misaligned(face_centers) || (((uintptr_t)binding) & (binding_is_i64 ? 7 : 3)))
         return fail(GDC_E_ARG, "bad arguments: pointers must be aligned to their element");
-    hipStream_t stream = (hipStream_t)stream_;
-    const gdc::OrderWorkspace w = gdc::carve_order(workspace, P);
-    const dim3 grid((unsigned)w.nchunks), block(gdc::BLOCK);
-    PROF_LAUNCH(gdc::k_ord_clear, dim3((gdc::ORD_HEAD + gdc::BLOCK - 1) / gdc::BLOCK), block, 0, stream, (int*)w.box);
-    LAUNCH_CHECK(GDC_E_HIP, "k_ord_clear");
-    PROF_LAUNCH(gdc::k_ord_bounds, grid, block, 0, stream, (int)P, (int)F, (const float*)xyz, binding, (int)binding_is_i64,
-                (const float*)face_centers, w.box);
-    LAUNCH_CHECK(GDC_E_HIP, "k_ord_bounds");
-    PROF_LAUNCH(gdc::k_ord_codes, grid, block, 0, stream, (int)P, (int)F, (const float*)xyz, binding, (int)binding_is_i64,
-                (const float*)face_centers, (const unsigned*)w.box, w.keys[0]);
-    LAUNCH_CHECK(GDC_E_HIP, "k_ord_codes");
-    for (int pass = 0; pass < gdc::PASSES; ++pass) {   // keys ping-pong between the two buffers; the last pass writes the rows to perm_out
-        const int shift = pass * gdc::RADIX_BITS, in = pass & 1, out = in ^ 1;
-        const bool last = pass == gdc::PASSES - 1;
-        int* totals = w.totals + pass * gdc::RADIX;
-        PROF_LAUNCH(gdc::k_ord_hist, grid, block, 0, stream, (int)P, w.nchunks, shift, (const unsigned*)w.keys[in], w.table, totals);
-        LAUNCH_CHECK(GDC_E_HIP, "k_ord_hist");
-        PROF_LAUNCH(gdc::k_ord_scan, dim3(gdc::RADIX), block, 0, stream, w.nchunks, w.table, (const int*)totals);
-        LAUNCH_CHECK(GDC_E_HIP, "k_ord_scan");
-        PROF_LAUNCH(gdc::k_ord_scatter, grid, block, 0, stream, (int)P, w.nchunks, shift, (const unsigned*)w.keys[in],
-                    (const int*)(pass == 0 ? nullptr : w.vals[in]), (const int*)w.table, last ? (unsigned*)nullptr : w.keys[out],
-                    last ? (int*)perm_out : w.vals[out]);
-        LAUNCH_CHECK(GDC_E_HIP, "k_ord_scatter");
-    }
-    return GDC_OK;
+    return enqueue_order(P, F, xyz, binding, binding_is_i64, face_centers, perm_out, workspace, (hipStream_t)stream_);
 }
 
 int gdc_permute(int32_t P, const void* perm, int32_t ntensors, const GdcTensor* tensors, void* stream_)
@@ -482,6 +489,33 @@ int gdc_permute(int32_t P, const void* perm, int32_t ntensors, const GdcTensor* 
     PROF_LAUNCH(gdc::k_dc_permute, dim3((unsigned)(((int64_t)P + GDC_ROWS - 1) / GDC_ROWS)), dim3(gdc::BLOCK), 0, (hipStream_t)stream_, t, (int)P,
                 (const int*)perm);
     LAUNCH_CHECK(GDC_E_HIP, "k_dc_permute");
+    return GDC_OK;
+}
+
+int64_t gdc_knn_workspace_bytes(int32_t P)
+{
+    if (P < 0 || P >= GDC_MAX_SPLATS) return -1;
+    const int64_t nboxes = ((int64_t)P + gdc::KNN_CHUNK - 1) / gdc::KNN_CHUNK;
+    return 16 * (int64_t)P + 32 * nboxes + 4 * (int64_t)P + gdc_order_workspace_bytes(P);
+}
+
+int gdc_knn3_dist2(int32_t P, const void* xyz, void* dist2_out, void* workspace, void* stream_)
+{
+    if (P < 0 || P >= GDC_MAX_SPLATS) return fail(GDC_E_ARG, "bad arguments: P = %d outside [0, %d)", (int)P, GDC_MAX_SPLATS);
+    if (P == 0) return GDC_OK;
+    if (!xyz || !dist2_out || !workspace) return fail(GDC_E_ARG, "bad arguments: NULL pointer");
+    if (misaligned(xyz) || misaligned(dist2_out) || (((uintptr_t)workspace) & 15))
+        return fail(GDC_E_ARG, "bad arguments: pointers must be aligned to their element, the workspace to 16 bytes");
+    hipStream_t stream = (hipStream_t)stream_;
+    const gdc::KnnWorkspace w = gdc::carve_knn(workspace, P);
+    const int rc = enqueue_order(P, 0, xyz, nullptr, 0, nullptr, w.perm, w.order, stream);
+    if (rc != GDC_OK) return rc;
+    const dim3 grid((unsigned)(((int64_t)P + gdc::BLOCK - 1) / gdc::BLOCK)), block(gdc::BLOCK);
+    PROF_LAUNCH(gdc::k_knn_gather, grid, block, 0, stream, (int)P, (const float*)xyz, (const int*)w.perm, w.pts, w.boxes);
+    LAUNCH_CHECK(GDC_E_HIP, "k_knn_gather");
+    PROF_LAUNCH(gdc::k_knn_search, grid, block, 0, stream, (int)P, w.nboxes, (const gdc::f4a*)w.pts, (const gdc::f4a*)w.boxes, (const int*)w.perm,
+                (float*)dist2_out);
+    LAUNCH_CHECK(GDC_E_HIP, "k_knn_search");
     return GDC_OK;
 }
 

@@ -96,7 +96,7 @@ class GaussianModel(_TrainingSetup):
             raise ValueError("binding_impl must be 'fused' or 'unfused'")
         self.binding_impl = binding_impl
 
-    # ---- parameter loading (synthetic stand-in for load_ply / create_from_pcd) ----------------
+    # ---- parameter loading: arrays, a point cloud (create_from_pcd), a PLY ----------------
     def load_arrays(self, arrs: Dict[str, np.ndarray], device="cuda", requires_grad: bool = True):
         """arrs uses the reference's leaf names (_xyz, _features_dc, _features_rest, _scaling, _rotation,
         _opacity, optional binding).  Like load_ply (:323) this activates the full SH degree."""
@@ -115,6 +115,47 @@ class GaussianModel(_TrainingSetup):
         # densification statistics, as training_setup allocates them (scene/gaussian_model.py:210-211)
         self.xyz_gradient_accum = torch.zeros((self._xyz.shape[0], 1), device=device)
         self.denom = torch.zeros((self._xyz.shape[0], 1), device=device)
+
+    def create_from_pcd(self, pcd, spatial_lr_scale: float, device="cuda"):
+        """scene/gaussian_model.py:172-206: a model from nothing.  Un-bound: `pcd` has `.points` and `.colors` (N, 3); the DC colours are
+        RGB2SH(colors) and every scale is log sqrt of the mean squared distance to the point's 3 nearest neighbours (knn.dist2_knn3: the exact
+        search of include/gdc.h on device tensors), clamped at 1e-7.  Bound (`pcd is None`, a model with a binding): one splat per entry of
+        `binding` at the face's origin, colours from the GLOBAL numpy stream as the reference draws them (np.random.random / 255: a seeded run
+        matches), scales log 1.  Both: identity rotations, opacity inverse_sigmoid(0.1), zero higher SH, zero max_radii2D; the leaves have the
+        layouts of load_arrays and `training_setup` works on the result.  `active_sh_degree` is left as it is (0 on a fresh model)."""
+        from . import knn
+
+        self.spatial_lr_scale = spatial_lr_scale
+        if pcd is None:
+            if self.binding is None:
+                raise ValueError("create_from_pcd(None, ...) needs a model with a binding")
+            n = self.binding.shape[0]
+            xyz = torch.zeros((n, 3), dtype=torch.float32, device=device)
+            color = torch.tensor(np.random.random((n, 3)) / 255.0).float()
+        else:
+            xyz = torch.tensor(np.asarray(pcd.points)).float().to(device)
+            color = (torch.tensor(np.asarray(pcd.colors)).float() - 0.5) / 0.28209479177387814   # utils/sh_utils.py: RGB2SH
+            n = xyz.shape[0]
+        # (the colours and the opacity constant are rounded on the host, once: a device divides by a scalar as a multiplication by its reciprocal
+        # and has its own log, and a model must not start an ulp away from where the same call puts it on the CPU)
+        color = color.to(device)
+        tenth = torch.full((1,), 0.1, dtype=torch.float32)
+        logit = float(torch.log(tenth / (1 - tenth)))   # utils/general_utils.py: inverse_sigmoid
+        if self.binding is None:
+            dist2 = torch.clamp_min(knn.dist2_knn3(xyz), 0.0000001)
+            scales = torch.log(torch.sqrt(dist2))[..., None].repeat(1, 3)
+        else:
+            scales = torch.zeros((n, 3), dtype=torch.float32, device=device)
+        rots = torch.zeros((n, 4), dtype=torch.float32, device=device)
+        rots[:, 0] = 1
+        leaves = {"_xyz": xyz, "_features_dc": color[:, None, :].contiguous(),
+                  "_features_rest": torch.zeros((n, (self.max_sh_degree + 1) ** 2 - 1, 3), dtype=torch.float32, device=device),
+                  "_scaling": scales, "_rotation": rots, "_opacity": torch.full((n, 1), logit, dtype=torch.float32, device=device)}
+        for k, t in leaves.items():
+            setattr(self, k, nn.Parameter(t.contiguous().requires_grad_(True)))
+        self.max_radii2D = torch.zeros((n,), device=device)
+        self.xyz_gradient_accum = torch.zeros((n, 1), device=device)
+        self.denom = torch.zeros((n, 1), device=device)
 
     def load_ply(self, path, device="cuda", spatial_sort: Optional[bool] = None, face_centers=None, **kwargs):
         """scene/gaussian_model.py:282-332: leaf tensors from the reference's PLY (binding -> int32).  `spatial_sort` (round 4: ON by

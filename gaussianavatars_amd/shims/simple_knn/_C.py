@@ -1,9 +1,16 @@
 """distCUDA2(points (N,3) f32) -> (N,) f32: mean SQUARED distance to the 3 nearest other points.
-Init-only and off the per-frame path, so this is chunked torch on whatever device the points live on."""
+Device tensors -- all the reference ever passes (scene/gaussian_model.py:191, `.cuda()`) -- go to knn.dist2_knn3: the exact search of
+include/gdc.h.  For CPU tensors the body below is chunked torch in the |a|^2 + |b|^2 - 2 a.b form.  That form cancels as soon as the cloud does
+not sit at the origin: on 600 points of randn * 1e-2 + 4 its relative error reaches 1.6 and 40 rows come back as exactly 0; at randn * 1e-3 + 50
+every row does (knn.dist2_knn3_composed is the difference form, good to 2e-7 on the same clouds)."""
 import torch
 
 
 def distCUDA2(points: torch.Tensor) -> torch.Tensor:
+    if points.device.type == "cuda":
+        from ... import knn
+
+        return knn.dist2_knn3(points)
     p = points.detach().float()
     n = p.shape[0]
     out = torch.empty(n, dtype=torch.float32, device=p.device)

@@ -51,6 +51,26 @@
  *                result does not depend on scheduling
  *     non-finite positions are outside the contract (numpy's answer is undefined); perm is still a permutation of 0..P-1, the same on
  *                every call, and nothing is stored out of range
+ *
+ * The nearest neighbours (additive to ABI 2): gdc_knn3_dist2() is simple-knn's distCUDA2 -- per point the mean squared distance to its 3
+ * nearest other points, what the reference initialises the scales of an unbound model from (scene/gaussian_model.py:190-192) -- as an EXACT
+ * search on that order.  Kernels only (the order's 15 launches, one gather, one search): no host read, no allocation, it can be recorded.
+ *     value      d2(i, j) = (dx*dx + dy*dy) + dz*dz with dx = x_i - x_j and so on, every operation rounded once in fp32, in that order (no
+ *                contraction).  dist2[i] = ((b0 + b1) + b2) / 3.0f over the three smallest d2(i, j), j != i, in ascending order.  j is left
+ *                out by INDEX, not by distance: a duplicate of point i is a neighbour at distance 0
+ *     few points P - 1 < 3: the mean over the P - 1 neighbours there are ((b0 + b1) / 2.0f, b0); P == 1 gives 0.0f; P == 0 launches nothing
+ *     exactness  the value equals what an fp32 brute force over all j with the arithmetic above gives; when two candidates tie for the
+ *                third place either is taken, the value being the same
+ *     method     the unbound order above; the positions gathered into it in one pass, with the box (per-axis min / max) of every run of
+ *                GDC_KNN_CHUNK consecutive sorted points; one query per lane in sorted order, so that a wave's 64 queries are neighbours
+ *                in space; the third-smallest distance to the +-3 neighbours in the sorted sequence bounds the answer from above; then the
+ *                chunks are walked, and one is scanned unless its box is farther than min(best[2], that bound) for every lane of the wave
+ *     pruning    the box distance is the same expression with the same roundings on the per-axis gaps (0 inside the box, p - hi or lo - p
+ *                otherwise).  Rounding is monotonic, so it is a lower bound of every fp32 d2 into that box, and `box_d2 > bound` skips
+ *                nothing that belongs to the answer.  This is why the library is compiled with -ffp-contract=off
+ *     output     scattered back through the permutation: dist2_out is in INPUT row order
+ *     no float atomics, no workgroup waits on another, two calls give the same bits
+ *     non-finite positions are outside the contract: every loop bound depends on P alone and nothing is stored out of range
  */
 #ifndef GDC_H
 #define GDC_H
@@ -62,6 +82,8 @@
 extern "C" {
 #endif
 
+/* stays 2: gdc_knn_workspace_bytes / gdc_knn3_dist2 are additive and no earlier entry changed.  A library built before them is caught by the
+ * loader's per-symbol check (_lib._load), not by this number. */
 #define GDC_ABI_VERSION 2
 #define GDC_OK 0
 #define GDC_E_ARG (-1)
@@ -74,6 +96,10 @@ extern "C" {
 #define GDC_ROWS 16
 /* P stays below this: an output row index (< 2 P) is an int32 */
 #define GDC_MAX_SPLATS (1 << 30)
+/* sorted points per box of gdc_knn3_dist2's search: a power of two, 2 ... 64 (a chunk is a run of lanes of one wave) */
+#ifndef GDC_KNN_CHUNK
+#define GDC_KNN_CHUNK 32
+#endif
 
 /* how the gather treats one tensor */
 #define GDC_COPY 0      /* every row: copy of the source row */
@@ -132,6 +158,16 @@ int gdc_morton_order(int32_t P, int32_t F, const void* xyz, const void* binding,
  * a row of two 4-byte elements; row_floats == 0 moves nothing; perm[r] outside [0, P) reads nothing and writes +0.0.  P == 0 or
  * ntensors == 0 launches nothing. */
 int gdc_permute(int32_t P, const void* perm, int32_t ntensors, const GdcTensor* tensors, void* stream);
+
+/* bytes of gdc_knn3_dist2's scratch buffer (16-byte aligned; its contents need not survive between calls): the sorted positions (16 bytes a
+ * point), the chunk boxes (32 bytes each), the permutation and the order's own scratch.  Monotonic in P; -1 when P is outside
+ * [0, GDC_MAX_SPLATS). */
+int64_t gdc_knn_workspace_bytes(int32_t P);
+
+/* dist2_out (P, fp32, input row order) = the mean squared distance of every row of xyz (P, 3) fp32 to its 3 nearest other rows, per the text
+ * above: 15 + 2 launches.  NULL pointers, P < 0 and P >= GDC_MAX_SPLATS return GDC_E_ARG before anything touches a device; P == 0 launches
+ * nothing (and needs no pointer). */
+int gdc_knn3_dist2(int32_t P, const void* xyz, void* dist2_out, void* workspace, void* stream);
 
 /* Optional per-kernel timing, as gop_profile_* (include/gop.h). */
 int gdc_profile_enable(int on);
