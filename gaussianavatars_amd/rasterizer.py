@@ -95,8 +95,16 @@ def set_fast_blend(enabled) -> int:
 # ---- poisoned state buffers (debugging aid, GSR_POISON_STATE=1) --------------------------------------
 # The three state buffers of a forward are fresh torch.empty allocations: whatever a kernel reads from them, an earlier kernel of the
 # same frame has to have written.  With this switch on they are filled with 0xFF bytes first (NaN as floats, 2^32 - 1 as counters), so
-# a word that is read before it is written shows up in the tests instead of depending on what the caching allocator recycled.
+# a word that is read before it is written shows up in the tests instead of depending on what the caching allocator recycled.  The
+# backward's own fresh allocations get the same fill: its scratch (colour / covariance gradients, then the bound entry's CSR rows), the
+# per-face gradient block and the gradient outputs -- a row, a face or a tail that no kernel writes reaches the caller as NaN.
 _poison_state = int(os.environ.get("GSR_POISON_STATE", "0"))
+
+
+def _poison(*tensors) -> None:
+    for t in tensors:
+        if t is not None and t.numel():
+            t.view(torch.uint8).fill_(0xFF)
 
 # Whether a backward can follow a forward is decided by the caller's GRAD MODE as well as by its inputs: inside Function.forward autograd is
 # always off and ctx.needs_input_grad only repeats the inputs' requires_grad flags -- render.py / fps_benchmark_*.py render nn.Parameters under
@@ -608,6 +616,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         g_sh_rest = torch.empty((P, M - 1, 3), **f32) if ctx.split else None
         g_scales = torch.empty((P, 3), **f32) if use_sr else None
         g_rot = torch.empty((P, 4), **f32) if use_sr else None
+        if _poison_state:
+            _poison(g_means3D, g_means2D, g_colors, g_opacity, g_cov3D, g_sh, g_sh_rest, g_scales, g_rot)
         stream = _lib.raw_stream(dev)
         with _lib.on_device(dev):
             rc = lib.gsr_backward_ex(C.byref(s), P, M, _ptr(means3D), _ptr(sh), _ptr(sh_rest), _ptr(colors_precomp), _ptr(scales),
@@ -756,6 +766,8 @@ class _RasterizeBound(torch.autograd.Function):
             b.binding, b.binding_is_i64, b.F = binding.data_ptr(), ctx.is64, F
             b.face_R, b.face_scale, b.face_center, b.face_quat = fR.data_ptr(), fs.data_ptr(), fc.data_ptr(), fq.data_ptr()
             b.slot, b.rows = slot.data_ptr(), scratch.data_ptr() + 4 * rows_at
+        if _poison_state:
+            _poison(scratch, d_face, g_xyz, g_means2D, g_dc, g_rest, g_op, g_ls, g_rot)
         stream = _lib.raw_stream(dev)
         with _lib.on_device(dev):
             rc = lib.gsr_backward_bound(C.byref(s), P, M, C.byref(b), _ptr(xyz), _ptr(sh_dc), _ptr(sh_rest), _ptr(opacity_logit), _ptr(log_scaling),

@@ -381,3 +381,71 @@ def face_sets():
     v, f, _ = bind_faces()
     out["bind F=40"] = (v.astype(np.float64), f)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------
+# the rasterizer's bound and leaves entries (tests/test_bound_entry_parity_gpu.py; conditions: tests/test_bound_entry_cases_cpu.py)
+# ------------------------------------------------------------------------------------------------------------------------------------------
+RASTER_NS = (1, 63, 257, 1000)
+RASTER_W, RASTER_H, RASTER_M = 96, 80, 16        # 6 x 5 tiles of 16 x 16; SH stored up to degree 3
+RASTER_BG = (0.2, 0.1, 0.3)
+# orbit_camera arguments of the two entries' cases: the camera sits inside the cloud, so splats and whole faces lie behind it (changed until the conditions of
+# tests/test_bound_entry_cases_cpu.py held for every case, as FACE_SEED was; the checks themselves are not loosened)
+RASTER_CAMERA = dict(bound=dict(r=0.25, fovy_deg=70.0, yaw_deg=20.0, pitch_deg=-10.0), leaves=dict(r=0.7, fovy_deg=100.0, yaw_deg=20.0, pitch_deg=-10.0))
+# GaussianRasterizationSettings.scale_modifier: identity frames leave exp(_scaling) up to e^2 world units, every pixel saturated by the first few
+RASTER_SCALE_MODIFIER = dict(bound=1.0, leaves=0.05)
+
+
+def identity_frames(F=BIND_F):
+    """Frames under which gab_bind_forward is the unbound model's activations, bit for bit (every fma of bind_math.h has an exact 0 or 1 operand)."""
+    return dict(face_R=np.tile(np.eye(3, dtype=np.float32), (F, 1, 1)), face_scale=np.ones((F, 1), np.float32), face_center=np.zeros((F, 3), np.float32),
+                face_quat=np.tile(np.array([1, 0, 0, 0], np.float32), (F, 1)))
+
+
+def raster_camera(entry):
+    from gaussianavatars_amd import synthetic as S
+
+    return S.orbit_camera(RASTER_W, RASTER_H, **RASTER_CAMERA[entry])
+
+
+@functools.lru_cache(maxsize=None)
+def raster_case(N, scaled_quat, entry="bound"):
+    """bind_case(N, scaled_quat) in front of a camera -> (leaves, binding, sh (N, 16, 3), grad_out_color (3, H, W), camera).
+    leaves: identity frames, every splat on face 0."""
+    leaves, binding, _ = bind_case(N, scaled_quat)
+    leaves = dict(leaves)
+    if entry == "leaves":
+        leaves.update(identity_frames())
+        binding = np.zeros_like(binding)
+    g = np.random.default_rng(600 + N)
+    sh = np.zeros((N, RASTER_M, 3), np.float32)
+    sh[:, 0] = g.normal(0.5, 0.5, (N, 3))
+    sh[:, 1:] = g.normal(0.0, 0.08, (N, RASTER_M - 1, 3))
+    gpix = g.normal(0.0, 1.0, (3, RASTER_H, RASTER_W)).astype(np.float32)
+    return leaves, binding, sh, gpix, raster_camera(entry)
+
+
+def world_values(leaves, binding):
+    """The four world-space tensors of a case: bind_eval in float64, rounded to fp32."""
+    zero = {k: np.zeros((1, n), np.float32) for k, n in (("xyz", 3), ("scaling", 3), ("rotation", 4), ("opacity", 1))}
+    r = bind_eval(leaves, binding, zero, torch.float64)
+    return {k: np.ascontiguousarray(r[k], np.float32) for k in BIND_OUTS}
+
+
+def raster_settings_args(cam, sh_degree, entry):
+    return dict(H=cam.image_height, W=cam.image_width, tanfovx=math.tan(cam.FoVx * 0.5), tanfovy=math.tan(cam.FoVy * 0.5), bg=np.asarray(RASTER_BG, np.float32),
+                scale_modifier=RASTER_SCALE_MODIFIER[entry], viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform, sh_degree=sh_degree, campos=cam.camera_center)
+
+
+def oracle_figures(oracle, N, scaled_quat, entry, sh_degree=3):
+    """The oracle's forward and backward on the fp32-rounded float64 world values of a case -> (radii (N,), binding, which rows of
+    G_w = (d xyz, d scaling, d rotation, d opacity) are not all zero)."""
+    leaves, binding, sh, gpix, cam = raster_case(N, scaled_quat, entry)
+    w = world_values(leaves, binding)
+    s = oracle.make_settings(**raster_settings_args(cam, sh_degree, entry))
+    st = oracle.forward(s, w["xyz"], sh, None, w["opacity"], w["scaling"], w["rotation"], None)
+    g = oracle.backward(s, st, gpix)
+    nz = np.zeros(N, bool)
+    for k in ("means3D", "scales", "rotations", "opacities"):
+        nz |= (g[k].reshape(N, -1) != 0).any(1)
+    return st.radii, binding, nz
