@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import threading
 from typing import NamedTuple, Optional
 
 import torch
@@ -21,8 +22,8 @@ from torch import nn
 
 from . import _host, _lib
 
-__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "rasterize_bound", "rasterize_leaves", "last_forward_info", "set_tile_culling", "deferred_count",
-           "get_tile_culling", "set_exact_scale_grad", "set_deterministic", "set_fast_blend", "set_poison_state"]
+__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "rasterize_bound", "rasterize_leaves", "last_forward_info",
+           "deferred_count", "set_tile_culling", "get_tile_culling", "set_exact_scale_grad", "set_deterministic", "set_fast_blend", "set_poison_state"]
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -63,6 +64,13 @@ def get_tile_culling() -> int:
 _exact_scale_grad = int(os.environ.get("GSR_EXACT_SCALE_GRAD", "0"))
 
 
+def set_exact_scale_grad(enabled: bool) -> bool:
+    """Process-wide switch; True multiplies dL/dscales by scale_modifier (the exact chain rule).  Returns the previous value."""
+    global _exact_scale_grad
+    prev, _exact_scale_grad = bool(_exact_scale_grad), int(bool(enabled))
+    return prev
+
+
 # ---- bit-reproducible backward (include/gsr.h: GsrSettings.deterministic) -------------------------
 _deterministic = int(os.environ.get("GSR_DETERMINISTIC", "0"))
 
@@ -101,18 +109,24 @@ def set_fast_blend(enabled) -> int:
 _poison_state = int(os.environ.get("GSR_POISON_STATE", "0"))
 
 
+def set_poison_state(enabled: bool) -> bool:
+    """Process-wide debugging switch; returns the previous value."""
+    global _poison_state
+    prev, _poison_state = bool(_poison_state), int(bool(enabled))
+    return prev
+
+
 def _poison(*tensors) -> None:
     for t in tensors:
         if t is not None and t.numel():
             t.view(torch.uint8).fill_(0xFF)
 
+
 # Whether a backward can follow a forward is decided by the caller's GRAD MODE as well as by its inputs: inside Function.forward autograd is
 # always off and ctx.needs_input_grad only repeats the inputs' requires_grad flags -- render.py / fps_benchmark_*.py render nn.Parameters under
 # torch.no_grad(), and render() hands every call a screen-space leaf that requires a gradient.  The entry points below note the mode around
 # .apply (thread-local); a direct .apply from elsewhere finds None and is treated as "a backward may follow".
-import threading as _threading
-
-_call_state = _threading.local()
+_call_state = threading.local()
 
 
 def _apply_noting_grad_mode(fn, *args):
@@ -129,29 +143,35 @@ def _backward_may_follow(needs) -> bool:
     return bool(needs) and (grad is None or grad)
 
 
-
-def set_poison_state(enabled: bool) -> bool:
-    """Process-wide debugging switch; returns the previous value."""
-    global _poison_state
-    prev, _poison_state = bool(_poison_state), int(bool(enabled))
-    return prev
-
-
-def set_exact_scale_grad(enabled: bool) -> bool:
-    """Process-wide switch; True multiplies dL/dscales by scale_modifier (the exact chain rule).  Returns the previous value."""
-    global _exact_scale_grad
-    prev, _exact_scale_grad = bool(_exact_scale_grad), int(bool(enabled))
-    return prev
-
-
 # ---- per-device running estimate of the binning capacity (instances per frame) -----------------
+# The capacity counts what the binning path produces: tile instances on the per-tile sort path, quadrant-stream entries on the production
+# path (include/gsr.h: gsr_binning_layout) -- one running estimate per path, keyed (device index, H, W, production path?).
 _CAP_QUANTUM = 1 << 16
 _capacity_hint: dict = {}
-_last_info: dict = {}
-
-
-_last_binning: list = [None]
 _forward_peak: list = [0]   # largest instance count of any forward since the caller last zeroed it (GraphedStep's warm-up sizes its capacity from it)
+_last_info: dict = {}
+_last_binning: list = [None]
+
+
+def _round_cap(n: int) -> int:
+    return max(_CAP_QUANTUM, (int(n) + _CAP_QUANTUM - 1) // _CAP_QUANTUM * _CAP_QUANTUM)
+
+
+def _first_cap(key, P: int, prod: bool) -> int:
+    """The capacity a frame is first tried with: the hint as it stands (a caller may have written any value), or a guess from the splat count."""
+    return _capacity_hint.get(key) or _round_cap((24 if prod else 8) * P)
+
+
+def _note_fitted(key, cap: int, I: int) -> None:
+    """A frame of I instances fitted `cap`.  Next frame: 25 % headroom over what this one needed, never shrinking below it."""
+    _capacity_hint[key] = max(_round_cap(int(I * 1.25) + 1), min(cap, _round_cap(2 * I + 1)))
+    _forward_peak[0] = max(_forward_peak[0], I)
+
+
+def _note_overflow(key, I: int) -> int:
+    """A frame of I instances did not fit (its kernels did nothing): -> the capacity to render it again with, which is the new hint."""
+    cap = _capacity_hint[key] = _round_cap(int(I * 1.25) + 1)
+    return cap
 
 
 def last_forward_info() -> dict:
@@ -173,10 +193,6 @@ def last_forward_info() -> dict:
 def release_last_state() -> None:
     """Drops the reference last_forward_info() keeps to the most recent frame's state buffers (they are otherwise freed when the next frame is rendered)."""
     _last_binning[0] = None
-
-
-def _round_cap(n: int) -> int:
-    return max(_CAP_QUANTUM, (int(n) + _CAP_QUANTUM - 1) // _CAP_QUANTUM * _CAP_QUANTUM)
 
 
 # ---- deferred instance count (include/gsr.h: GsrSettings.deferred_count) -------------------------
@@ -229,6 +245,7 @@ class _Deferred:
 
 
 _free_slots = list(range(_lib.GSR_COUNT_SLOTS - 1, -1, -1))
+_deferred: Optional[_Deferred] = None   # the state of the innermost open `deferred_count` context (read by every forward at call time)
 
 # ---- the count wait of an eager frame, moved behind the rest of the call's host work (round 4) ---------------------------------------------
 # gsr_forward launches the frame's eight kernels and then spins until the fifth has posted the instance count -- ~18 us per step during which
@@ -277,10 +294,9 @@ def _finish_late(pend) -> bool:
     I = int(n.value)
     if I > cap:
         lib.gsr_count_slot_overflow(slot, None, 1)   # (the device left its sticky mark: this slot's only reader is this function)
-        _capacity_hint[key] = _round_cap(int(I * 1.25) + 1)
+        _note_overflow(key, I)
         return False
-    _capacity_hint[key] = max(_round_cap(int(I * 1.25) + 1), min(cap, _round_cap(2 * I + 1)))
-    _forward_peak[0] = max(_forward_peak[0], I)
+    _note_fitted(key, cap, I)
     _last_info["num_rendered"] = I
     return True
 
@@ -296,7 +312,7 @@ def _camera_tensor(t):
     """A contiguous fp32 device tensor with `t`'s values, or None (a host tensor: not this entry's case).  fps_benchmark_demo.py:30-31 and scene/cameras.py:44-46
     hand the rasterizer TRANSPOSED VIEWS (`.T`, `.transpose(0, 1)`) that live as long as the camera: copying them in every frame is a launch per matrix, so the copy
     is made once per (object, version) and kept beside the camera's tensor."""
-    if t.is_cuda and t.dtype is torch.float32 and t.is_contiguous():
+    if _is_plain(t):
         return t
     if not t.is_cuda:
         return None
@@ -336,20 +352,18 @@ def _native_leaves_entry(H, xyz, means2D, sh_dc, sh_rest, opacity_logit, log_sca
     prod = _binning_layout(lib, 0, Ww, Hh, P, tc).path == 1
     key = (dev.index, Hh, Ww, prod)
     late = _late_slot(dev, _lib.raw_stream(dev))
+    cap = _first_cap(key, P, prod)
     replays = 0
     while True:
-        cap = _capacity_hint.get(key) or _round_cap((24 if prod else 8) * P)
         r = H.rasterize_bound(xyz, means2D, sh_dc, sh_rest, opacity_logit, log_scaling, rotation, face_R, face_scale, face_center, face_quat, binding, slot, face_begin,
                               bg, vm, pm, cp, Hh, Ww, float(rs.tanfovx), float(rs.tanfovy), float(rs.scale_modifier), int(rs.sh_degree), 0, tc,
                               int(_exact_scale_grad), int(_deterministic), int(_fast_blend), cap, late)
         I = r.num_rendered
         if r.fitted:
             break
-        _capacity_hint[key] = _round_cap(int(I * 1.25) + 1)   # the frame did not fit: its kernels did nothing, the node just made is dropped un-walked
+        cap = _note_overflow(key, I)   # the frame did not fit: its kernels did nothing, the node just made is dropped un-walked
         replays += 1
-    _capacity_hint[key] = max(_round_cap(int(I * 1.25) + 1), min(cap, _round_cap(2 * I + 1)))
-    if I > _forward_peak[0]:
-        _forward_peak[0] = I
+    _note_fitted(key, cap, I)
     _last_info.update(num_rendered=I, capacity=cap, replays=replays, tile_culling=bool(tc), production_binning=prod, forward_only=bool(r.forward_only),
                       binning_path=r.path, rank_bands=r.nbands, bound=True, native_host=True)
     # (state allocation, byte offset of its binning part): last_forward_info() reads the header on request.  This keeps the last frame's ONE state
@@ -389,7 +403,6 @@ def _apply_late(fn, *args):
                 _last_info["replays"] = replays
             return out
         replays += 1   # the frame did not fit: its kernels did nothing, the node just made is dropped un-walked
-_deferred: Optional[_Deferred] = None
 
 
 class deferred_count:
@@ -427,7 +440,7 @@ def _ptr(t: Optional[torch.Tensor]):
 
 
 def _f32c(t: torch.Tensor, name: str) -> torch.Tensor:
-    if t.is_cuda and t.dtype is torch.float32 and t.is_contiguous():
+    if _is_plain(t):
         return t
     if not t.is_cuda:
         raise RuntimeError(f"{name} must be a device tensor (got {t.device}); the MI355X rasterizer has no CPU path")
@@ -451,6 +464,14 @@ def _make_settings(rs: GaussianRasterizationSettings, keep: list) -> _lib.GsrSet
         t = _f32c(getattr(rs, field), field)
         keep.append(t)
         setattr(s, field, t.data_ptr())
+    return s
+
+
+def _backward_settings(ctx, keep: list) -> _lib.GsrSettings:
+    """The settings of ctx's frame for its backward: the state buffers were laid out for the forward's tile_culling, the accumulators
+    zero-filled for its deterministic mode and the per-splat records written for its fast_blend, whatever the switches say by now."""
+    s = _make_settings(ctx.raster_settings, keep)
+    s.tile_culling, s.deterministic, s.fast_blend, s.forward_only = ctx.tile_culling, ctx.deterministic, ctx.fast_blend, 0
     return s
 
 
@@ -483,6 +504,72 @@ def _binning_layout(lib, cap, W, H, P, mode):
     return hit
 
 
+class _Frame(NamedTuple):
+    color: torch.Tensor
+    radii: torch.Tensor
+    visible: torch.Tensor   # render()'s visibility_filter (radii > 0) as the forward wrote it: a bool view of the state buffer, no comparison launch
+    geom: torch.Tensor
+    binning: torch.Tensor
+    img: torch.Tensor
+    cap: int
+    I: int                  # instances binned; the capacity where the count is not awaited inside the call (the backward takes it as the bound)
+
+
+def _launch_frame(lib, s, dev, P, bound, call, on_error) -> _Frame:
+    """One frame of either autograd entry: outputs and state buffers, the capacity, the form of the count wait (a recording's slot, the
+    late slot of _apply_late, or blocking), the native call -- again with a larger binning buffer while it reports GSR_E_CAPACITY -- and
+    the bookkeeping last_forward_info() reads.  `call(color, radii, geom, binning, cap, img, n_host, stream) -> rc` is the entry's native
+    forward on its own inputs; `on_error(rc, msg)` raises the entry's error."""
+    H, W = s.image_height, s.image_width
+    gl, il = _layouts(lib, P, W, H)
+    u8 = dict(dtype=torch.uint8, device=dev)
+    color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+    radii = torch.empty((P,), dtype=torch.int32, device=dev)
+    geom = torch.empty(gl.total, **u8)
+    img = torch.empty(il.total, **u8)
+    if _poison_state:
+        geom.fill_(0xFF), img.fill_(0xFF)
+    prod = _binning_layout(lib, 0, W, H, P, int(s.tile_culling)).path == 1
+    key = (dev.index, H, W, prod)
+    cap = _first_cap(key, P, prod)
+    defer = _deferred
+    stream = _lib.raw_stream(dev)
+    late_slot = -1
+    if defer is not None:   # fixed capacity, count posted to a persistent slot, nothing waits (see deferred_count)
+        cap, s.deferred_count = defer.capacity, defer.take() + 1
+    elif getattr(_call_state, "late", False):   # (_apply_late) the count is awaited after this call's host work, not inside it
+        late_slot = _late_slot(dev, stream)
+        if late_slot >= 0:
+            s.deferred_count = late_slot + 1
+    n_host = C.c_int64(0)
+    replays = 0
+    with _lib.on_device(dev):
+        while True:
+            bl = _binning_layout(lib, cap, W, H, P, int(s.tile_culling))
+            binning = torch.empty(bl.total, **u8)
+            if _poison_state:
+                binning.fill_(0xFF)
+            rc = call(color, radii, geom, binning, cap, img, n_host, stream)
+            if rc == _lib.GSR_OK:
+                break
+            if rc != _lib.GSR_E_CAPACITY:
+                on_error(rc, _lib.gsr_error())
+            cap = _note_overflow(key, n_host.value)   # (the blocking form only: the other two do not read the count here)
+            replays += 1
+    I = int(n_host.value)
+    waited = defer is None and late_slot < 0
+    if late_slot >= 0:   # as a recording's frame; _finish_late does the bookkeeping
+        _call_state.pending = (late_slot, int(lib.gsr_last_forward_seq()), cap, key, stream, dev)
+    if waited:
+        _note_fitted(key, cap, I)
+    else:
+        I = cap      # unknown until the kernels have run
+    _last_info.update(num_rendered=I if waited else -1, capacity=cap, replays=replays, tile_culling=bool(s.tile_culling), production_binning=prod, forward_only=bool(s.forward_only),
+                      binning_path=int(bl.path), rank_bands=int(bl.nbands), bound=bound)   # 0 rank path, 1 depth-ordered scatter, 2 per-tile sort (include/gsr.h)
+    _last_binning[0] = binning
+    return _Frame(color, radii, geom[gl.visible: gl.visible + P].view(torch.bool), geom, binning, img, cap, I)
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest=None):
@@ -497,7 +584,6 @@ class _RasterizeGaussians(torch.autograd.Function):
         if means3D.dim() != 2 or means3D.shape[1] != 3:
             raise RuntimeError("means3D must have dimensions (num_points, 3)")
         P = means3D.shape[0]
-        H, W = s.image_height, s.image_width
         sh = _f32c(sh, "shs") if sh.numel() else sh
         colors_precomp = _f32c(colors_precomp, "colors_precomp") if colors_precomp.numel() else colors_precomp
         opacities = _f32c(opacities, "opacities")
@@ -513,68 +599,22 @@ class _RasterizeGaussians(torch.autograd.Function):
             sh_rest = torch.empty(0, device=dev)
         M = (int(sh.shape[1]) + (int(sh_rest.shape[1]) if split else 0)) if sh.numel() else 0
 
-        gl, il = _layouts(lib, P, W, H)
-        u8 = dict(dtype=torch.uint8, device=dev)
-        color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
-        radii = torch.empty((P,), dtype=torch.int32, device=dev)
-        geom = torch.empty(gl.total, **u8)
-        img = torch.empty(il.total, **u8)
-        if _poison_state:
-            geom.fill_(0xFF), img.fill_(0xFF)
+        def call(color, radii, geom, binning, cap, img, n_host, stream):
+            return lib.gsr_forward_ex(C.byref(s), P, M, _ptr(means3D), _ptr(sh), _ptr(sh_rest), _ptr(colors_precomp), _ptr(opacities),
+                                      _ptr(scales), _ptr(rotations), _ptr(cov3Ds_precomp), _ptr(color), _ptr(radii),
+                                      _ptr(geom), _ptr(binning), cap, _ptr(img), C.byref(n_host), stream)
 
-        # the capacity counts what the binning path produces: tile instances on the per-tile sort path, quadrant-stream entries
-        # on the production path (include/gsr.h: gsr_binning_layout) -- one running estimate per path
-        prod = _binning_layout(lib, 0, W, H, P, int(s.tile_culling)).path == 1
-        key = (dev.index, H, W, prod)
-        cap = _capacity_hint.get(key) or _round_cap((24 if prod else 8) * P)
-        defer = _deferred
-        stream = _lib.raw_stream(dev)
-        late_slot = -1
-        if defer is not None:   # fixed capacity, count posted to a persistent slot, nothing waits (see deferred_count)
-            cap, s.deferred_count = defer.capacity, defer.take() + 1
-        elif getattr(_call_state, "late", False):   # (_apply_late) the count is awaited after this call's host work, not inside it
-            late_slot = _late_slot(dev, stream)
-            if late_slot >= 0:
-                s.deferred_count = late_slot + 1
-        n_host = C.c_int64(0)
-        replays = 0
-        with _lib.on_device(dev):
-            while True:
-                bl = _binning_layout(lib, cap, W, H, P, int(s.tile_culling))
-                binning = torch.empty(bl.total, **u8)
-                if _poison_state:
-                    binning.fill_(0xFF)
-                rc = lib.gsr_forward_ex(C.byref(s), P, M, _ptr(means3D), _ptr(sh), _ptr(sh_rest), _ptr(colors_precomp), _ptr(opacities),
-                                     _ptr(scales), _ptr(rotations), _ptr(cov3Ds_precomp), _ptr(color), _ptr(radii),
-                                     _ptr(geom), _ptr(binning), cap, _ptr(img), C.byref(n_host), stream)
-                if rc == _lib.GSR_E_CAPACITY:
-                    cap = _round_cap(int(n_host.value * 1.25) + 1)
-                    replays += 1
-                    continue
-                if rc != _lib.GSR_OK:
-                    msg = _lib.gsr_error()
-                    if "provide" in msg:  # the two argument-contract errors are plain Exceptions upstream
-                        raise Exception(msg)
-                    if raster_settings.debug:   # upstream's debug mode: the failing call's arguments go to a file before the error is raised
-                        _debug_dump("snapshot_fw.dump", (raster_settings.bg, means3D, colors_precomp, opacities, scales, rotations, raster_settings.scale_modifier,
-                                                         cov3Ds_precomp, raster_settings.viewmatrix, raster_settings.projmatrix, raster_settings.tanfovx,
-                                                         raster_settings.tanfovy, raster_settings.image_height, raster_settings.image_width, sh,
-                                                         raster_settings.sh_degree, raster_settings.campos, raster_settings.prefiltered))
-                    raise RuntimeError(f"gsr_forward failed ({rc}): {msg}")
-                break
-        I = int(n_host.value)
-        if late_slot >= 0:
-            _call_state.pending = (late_slot, int(lib.gsr_last_forward_seq()), cap, key, stream, dev)
-            I = cap      # as a recording's frame: the backward takes the capacity as the bound; _finish_late does the bookkeeping
-        elif defer is not None:
-            I = cap      # unknown until the kernels have run: the backward takes the capacity as the bound
-        else:   # next frame: 25 % headroom over what this one needed, never shrinking below it
-            _capacity_hint[key] = max(_round_cap(int(I * 1.25) + 1), min(cap, _round_cap(2 * I + 1)))
-            _forward_peak[0] = max(_forward_peak[0], I)
-        _last_info.update(num_rendered=I if (defer is None and late_slot < 0) else -1, capacity=cap, replays=replays, tile_culling=bool(s.tile_culling), production_binning=prod, forward_only=bool(s.forward_only),
-                          binning_path=int(bl.path), rank_bands=int(bl.nbands), bound=False)   # 0 rank path, 1 depth-ordered scatter, 2 per-tile sort (include/gsr.h)
-        _last_binning[0] = binning
+        def on_error(rc, msg):
+            if "provide" in msg:  # the two argument-contract errors are plain Exceptions upstream
+                raise Exception(msg)
+            if raster_settings.debug:   # upstream's debug mode: the failing call's arguments go to a file before the error is raised
+                _debug_dump("snapshot_fw.dump", (raster_settings.bg, means3D, colors_precomp, opacities, scales, rotations, raster_settings.scale_modifier,
+                                                 cov3Ds_precomp, raster_settings.viewmatrix, raster_settings.projmatrix, raster_settings.tanfovx,
+                                                 raster_settings.tanfovy, raster_settings.image_height, raster_settings.image_width, sh,
+                                                 raster_settings.sh_degree, raster_settings.campos, raster_settings.prefiltered))
+            raise RuntimeError(f"gsr_forward failed ({rc}): {msg}")
 
+        color, radii, visible, geom, binning, img, cap, I = _launch_frame(lib, s, dev, P, False, call, on_error)
         ctx.raster_settings = raster_settings
         ctx.tile_culling = int(s.tile_culling)    # the state buffers are laid out for this mode
         ctx.deterministic = int(s.deterministic)  # and the accumulators zero-filled for this one
@@ -584,8 +624,6 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.M = M
         ctx.split = split
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img, sh_rest)
-        # render()'s visibility_filter (radii > 0) as the forward wrote it: a bool view of the state buffer, no comparison launch
-        visible = geom[gl.visible: gl.visible + P].view(torch.bool)
         ctx.mark_non_differentiable(radii, visible)
         return color, radii, visible
 
@@ -598,11 +636,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         rs = ctx.raster_settings
         dev = means3D.device
         keep: list = []
-        s = _make_settings(rs, keep)
-        s.tile_culling = ctx.tile_culling
-        s.deterministic = ctx.deterministic
-        s.fast_blend = ctx.fast_blend
-        s.forward_only = 0
+        s = _backward_settings(ctx, keep)
         P, M = means3D.shape[0], ctx.M
         f32 = dict(dtype=torch.float32, device=dev)
         grad_out_color = _f32c(grad_out_color, "grad_out_color")
@@ -668,58 +702,17 @@ class _RasterizeBound(torch.autograd.Function):
                 raise RuntimeError("the bound rasterizer needs the binding's per-face CSR (binding.binding_csr) for this binding and mesh")
             b.binding, b.binding_is_i64, b.F = binding.data_ptr(), int(binding.dtype == torch.int64), F
             b.face_R, b.face_scale, b.face_center, b.face_quat = fR.data_ptr(), fs.data_ptr(), fc.data_ptr(), fq.data_ptr()
-        H, W = s.image_height, s.image_width
         M = 1 + int(sh_rest.shape[1])
-        gl, il = _layouts(lib, P, W, H)
-        u8 = dict(dtype=torch.uint8, device=dev)
-        color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
-        radii = torch.empty((P,), dtype=torch.int32, device=dev)
-        geom = torch.empty(gl.total, **u8)
-        img = torch.empty(il.total, **u8)
-        if _poison_state:
-            geom.fill_(0xFF), img.fill_(0xFF)
-        prod = _binning_layout(lib, 0, W, H, P, int(s.tile_culling)).path == 1
-        key = (dev.index, H, W, prod)
-        cap = _capacity_hint.get(key) or _round_cap((24 if prod else 8) * P)
-        defer = _deferred
-        stream = _lib.raw_stream(dev)
-        late_slot = -1
-        if defer is not None:   # fixed capacity, count posted to a persistent slot, nothing waits (see deferred_count)
-            cap, s.deferred_count = defer.capacity, defer.take() + 1
-        elif getattr(_call_state, "late", False):   # (_apply_leaves_entry) the count is awaited after this call's host work, not inside it
-            late_slot = _late_slot(dev, stream)
-            if late_slot >= 0:
-                s.deferred_count = late_slot + 1
-        n_host = C.c_int64(0)
-        replays = 0
-        with _lib.on_device(dev):
-            while True:
-                bl = _binning_layout(lib, cap, W, H, P, int(s.tile_culling))
-                binning = torch.empty(bl.total, **u8)
-                if _poison_state:
-                    binning.fill_(0xFF)
-                rc = lib.gsr_forward_bound(C.byref(s), P, M, C.byref(b), _ptr(xyz), _ptr(sh_dc), _ptr(sh_rest), _ptr(opacity_logit),
-                                           _ptr(log_scaling), _ptr(rotation), _ptr(color), _ptr(radii), _ptr(geom), _ptr(binning), cap,
-                                           _ptr(img), C.byref(n_host), stream)
-                if rc == _lib.GSR_E_CAPACITY:
-                    cap = _round_cap(int(n_host.value * 1.25) + 1)
-                    replays += 1
-                    continue
-                if rc != _lib.GSR_OK:
-                    raise RuntimeError(f"gsr_forward_bound failed ({rc}): {_lib.gsr_error()}")
-                break
-        I = int(n_host.value)
-        if late_slot >= 0:
-            _call_state.pending = (late_slot, int(lib.gsr_last_forward_seq()), cap, key, stream, dev)
-            I = cap      # as a recording's frame: the backward takes the capacity as the bound; _finish_late does the bookkeeping
-        elif defer is not None:
-            I = cap      # unknown until the kernels have run: the backward takes the capacity as the bound
-        else:
-            _capacity_hint[key] = max(_round_cap(int(I * 1.25) + 1), min(cap, _round_cap(2 * I + 1)))
-            _forward_peak[0] = max(_forward_peak[0], I)
-        _last_info.update(num_rendered=I if (defer is None and late_slot < 0) else -1, capacity=cap, replays=replays, tile_culling=bool(s.tile_culling), production_binning=prod, forward_only=bool(s.forward_only),
-                          binning_path=int(bl.path), rank_bands=int(bl.nbands), bound=True)
-        _last_binning[0] = binning
+
+        def call(color, radii, geom, binning, cap, img, n_host, stream):
+            return lib.gsr_forward_bound(C.byref(s), P, M, C.byref(b), _ptr(xyz), _ptr(sh_dc), _ptr(sh_rest), _ptr(opacity_logit),
+                                         _ptr(log_scaling), _ptr(rotation), _ptr(color), _ptr(radii), _ptr(geom), _ptr(binning), cap,
+                                         _ptr(img), C.byref(n_host), stream)
+
+        def on_error(rc, msg):
+            raise RuntimeError(f"gsr_forward_bound failed ({rc}): {msg}")
+
+        color, radii, visible, geom, binning, img, cap, I = _launch_frame(lib, s, dev, P, True, call, on_error)
         ctx.raster_settings = raster_settings
         ctx.tile_culling, ctx.deterministic, ctx.fast_blend = int(s.tile_culling), int(s.deterministic), int(s.fast_blend)
         ctx.num_rendered, ctx.capacity, ctx.M, ctx.F = I, cap, M, F
@@ -727,7 +720,6 @@ class _RasterizeBound(torch.autograd.Function):
         ctx.csr = csr
         ctx.unbound = binding is None
         ctx.save_for_backward(xyz, sh_dc, sh_rest, opacity_logit, log_scaling, rotation, fR, fs, fc, fq, binding, radii, geom, binning, img)
-        visible = geom[gl.visible: gl.visible + P].view(torch.bool)
         ctx.mark_non_differentiable(radii, visible)
         return color, radii, visible
 
@@ -740,8 +732,7 @@ class _RasterizeBound(torch.autograd.Function):
         xyz, sh_dc, sh_rest, opacity_logit, log_scaling, rotation, fR, fs, fc, fq, binding, radii, geom, binning, img = ctx.saved_tensors
         dev = xyz.device
         keep: list = []
-        s = _make_settings(ctx.raster_settings, keep)
-        s.tile_culling, s.deterministic, s.fast_blend, s.forward_only = ctx.tile_culling, ctx.deterministic, ctx.fast_blend, 0
+        s = _backward_settings(ctx, keep)
         P, M, F = xyz.shape[0], ctx.M, ctx.F
         f32 = dict(dtype=torch.float32, device=dev)
         if P == 0:   # everything pruned: no splat, no gradient -- zeros of the right shapes (the native entries have nothing to point at)

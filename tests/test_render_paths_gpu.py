@@ -390,3 +390,60 @@ def test_late_count_wait_equals_the_blocking_form_and_replays_a_frame_that_did_n
         assert bool(torch.isfinite(gu._xyz.grad).all()) and float(gu._xyz.grad.abs().max()) > 0
     finally:
         R._late_count = prev
+
+
+@pytest.mark.fast_blend
+def test_leaves_entry_and_module_share_one_frame_routine():
+    """The two autograd entries launch a frame through one routine (rasterizer._launch_frame): the same un-bound scene through rasterize_leaves
+    (the Python twin: compiled host off) and through the reference-shaped module on the activated tensors, each with the blocking and the late
+    count wait, state buffers poisoned, each from an empty capacity hint.  Same radii bits in all four frames, the same image bits within an
+    entry, and the same bookkeeping in last_forward_info() -- but for `bound`, which names the entry."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from gaussianavatars_amd import _host
+    from gaussianavatars_amd import rasterizer as R
+
+    dev = torch.device("cuda:0")
+    g, cam = _scene(dev)
+    bg = torch.tensor([0.2, 0.1, 0.3], device=dev)
+    rs = R.GaussianRasterizationSettings(208, 176, math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5), bg, 1.0, cam.world_view_transform,
+                                         cam.full_proj_transform, 3, cam.camera_center, False, False)
+    dc, rest = g.get_features_split
+    rast = R.GaussianRasterizer(rs)
+
+    def leaves():
+        return R.rasterize_leaves(g._xyz, torch.zeros_like(g._xyz, requires_grad=True), dc, rest, g._opacity, g._scaling, g._rotation, rs)[:2]
+
+    def module():
+        return rast(means3D=g.get_xyz, means2D=torch.zeros_like(g._xyz, requires_grad=True), opacities=g.get_opacity, shs=dc, shs_rest=rest,
+                    scales=g.get_scaling, rotations=g.get_rotation)
+
+    same = ("num_rendered", "capacity", "replays", "tile_culling", "production_binning", "binning_path", "rank_bands", "forward_only")
+    prev_late, hint = R._late_count, dict(R._capacity_hint)
+    prev_poison = R.set_poison_state(True)
+    prev_host = _host.set_enabled(False)
+    out = {}
+    try:
+        for what, entry in (("leaves", leaves), ("module", module)):
+            for late in (False, True):
+                R._late_count = late
+                R._capacity_hint.clear()
+                img, radii = entry()
+                info = R.last_forward_info()
+                out[what, late] = (img.detach().clone(), radii.clone(), info)
+                print(what, "late" if late else "blocking", {k: info[k] for k in same + ("bound",)})
+    finally:
+        _host.set_enabled(prev_host)
+        R.set_poison_state(prev_poison)
+        R._late_count = prev_late
+        R._capacity_hint.clear()
+        R._capacity_hint.update(hint)
+    first = out["leaves", False]
+    assert first[2]["num_rendered"] > 0 and first[2]["forward_only"] is False
+    for (what, late), (img, radii, info) in out.items():
+        print(what, "late" if late else "blocking", "radii that differ from the first frame's:", int((radii != first[1]).sum()))
+    for (what, late), (img, radii, info) in out.items():
+        assert torch.equal(radii, first[1]), (what, late)
+        assert torch.equal(img.view(torch.int32), out[what, False][0].view(torch.int32)), (what, late)
+        assert {k: info[k] for k in same} == {k: first[2][k] for k in same}, (what, late, info)
+        assert info["bound"] is (what == "leaves"), (what, late)
