@@ -360,8 +360,8 @@ gls_error = partial(last_error, "gls")
 
 
 # ------------------------------------------------------------------------------------------------
-# libgmr_hip.so : the mesh overlay's triangle rasterizer and antialias (include/gmr.h).  Loaded only by mesh_raster.py:
-# the splat path never maps it.
+# libgmr_hip.so : the mesh overlay's triangle rasterizer and antialias (include/gmr.h).  Loaded only by mesh_raster.py and
+# mesh_renderer.py: the splat path never maps it.
 # ------------------------------------------------------------------------------------------------
 GMR_LIB_PATH = _lib_path("gmr")
 GMR_SYMBOLS = {
@@ -371,18 +371,39 @@ GMR_SYMBOLS = {
     "gmr_rasterize": (C.c_int, [C.c_int32] * 5 + [_P, _P, _P, _P, _P]),
     "gmr_antialias": (C.c_int, [C.c_int32] * 6 + [_P] * 7),
 }
-GMR_ABI_VERSION = 1
+GMR_ABI_VERSION = 2
 GMR_MAX_TRIANGLES = (1 << 24) - 1   # include/gmr.h: triangle_id + 1 is stored as an exact float
 
 LIBS["gmr"] = LibSpec("gmr", GMR_LIB_PATH, GMR_SYMBOLS, GMR_ABI_VERSION)
+
+# ABI 2, include/gmr_overlay.h (which gmr.h includes): the shaded overlay of mesh_renderer.py.  A table of its own because GMR_SYMBOLS is
+# pinned to the five declarations of gmr.h itself (tests/test_mesh_raster_cpu.py), like LIBS to its six tags; gmr() checks both tables, so
+# a library built before these entries raises at load time
+GMR_LIGHT_CONSTANT, GMR_LIGHT_FRONT = 0, 1   # include/gmr_overlay.h
+GMR_MAT_ROWS, GMR_MAT_CAMERA = 0, 1
+GMR_MAX_MAPS = 4
+
+
+class GmrMap(C.Structure):
+    """include/gmr_overlay.h: GmrMap"""
+    _fields_ = [("src", _P), ("dst", _P), ("C", C.c_int32)]
+
+
+GMR_OVERLAY_SYMBOLS = {
+    "gmr_mesh_prepare": (C.c_int, [C.c_int32] * 3 + [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P]),
+    "gmr_mesh_shade": (C.c_int, [C.c_int32] * 4 + [_P, _P, _P, C.c_int32, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P]),
+    "gmr_resize_flip": (C.c_int, [C.c_int32] * 6 + [C.POINTER(GmrMap), _P]),
+    "gmr_compose_overlay": (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_float, C.c_float, _P, _P, _P]),
+}
 _gmr = None
 
 
 def gmr():
-    """The mesh rasterizer library; raises (never falls back) when it is not built."""
+    """The mesh rasterizer library; raises (never falls back) when it is not built or lacks an entry of either table."""
     global _gmr
     if _gmr is None:
-        _gmr = _load(LIBS["gmr"])
+        spec = LIBS["gmr"]
+        _gmr = _load(spec._replace(symbols={**spec.symbols, **GMR_OVERLAY_SYMBOLS}))
     return _gmr
 
 

@@ -431,3 +431,5 @@ int gmr_antialias(int32_t B, int32_t V, int32_t F, int32_t H, int32_t W, int32_t
 }
 
 }  // extern "C"
+
+#include "gmr_overlay.h"   // ABI 2: prepare, shade, resize / flip, compose (include/gmr_overlay.h)

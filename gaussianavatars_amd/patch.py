@@ -13,6 +13,7 @@ What is rebound (attribute names, lazy initialisation and autograd connectivity 
     GaussianModel.get_features_split (new)       the two SH leaf tensors, read in place by gsr_forward_ex (no per-frame cat, :152-156)
     gaussian_renderer.render (optional)          gaussian_renderer/__init__.py:19-101   -> the mirror with the split-SH / leaf fast paths
     GaussianModel.densify_and_prune              scene/gaussian_model.py:501-515        -> gdc_plan + gdc_emit (densify.py; GAA_FUSED_DENSIFY=0 opts out)
+    NVDiffRenderer.render_mesh / render_from_camera   mesh_renderer/__init__.py:183-274   -> mesh_renderer.py (include/gmr_overlay.h; GAA_FUSED_OVERLAY=0 opts out)
 
 `patch_classes` works on any class pair with the reference's attribute names; the repository's own mirror classes
 (gaussianavatars_amd/gaussian_model.py) are written in composed torch like the reference and go through the very same
@@ -305,7 +306,8 @@ def unpatch_classes(*classes) -> None:
             setattr(cls, name, orig)
             del _ORIG[(cls, name)]
     for cls in classes:
-        for flag in ("_gaa_patched", "_gaa_patched_flame", "_gaa_patched_head", "_gaa_patched_base", "_gaa_patched_stats", "_gaa_patched_optimizer"):
+        for flag in ("_gaa_patched", "_gaa_patched_flame", "_gaa_patched_head", "_gaa_patched_base", "_gaa_patched_stats", "_gaa_patched_optimizer",
+                     "_gaa_patched_overlay"):
             if flag in cls.__dict__:
                 delattr(cls, flag)
         if isinstance(cls.__dict__.get("get_features_split"), property) and cls.__dict__["get_features_split"].fget is _get_features_split:
@@ -329,8 +331,10 @@ def patch_reference(reference_root: str | None = None, fast_render: bool = True,
        -> the fused kernels of include/gls.h (train.py:131-132,198 unchanged).
     7. (GAA_FUSED_ADAM=0 opts out) patch_optimizer: the torch.optim.Adam that `training_setup` builds becomes an optim.FusedAdam, so
        train.py:209's `gaussians.optimizer.step()` is one launch of include/gop.h.
+    8. (GAA_FUSED_OVERLAY=0 opts out) adopt_mesh_overlay: `NVDiffRenderer.render_mesh` / `render_from_camera` (render.py --render_mesh, the
+       viewers' show_mesh) run on mesh_renderer.py: six launches instead of the composed torch around rasterize and antialias.
     Returns {'shims': [...], 'classes': [...], 'render': bool, 'pinned_cpus': [...] | None, 'backward_seed': bool, 'loss': [...],
-    'optimizer': [...]}.  Call it before the entry script imports `render`."""
+    'optimizer': [...], 'overlay': [...]}.  Call it before the entry script imports `render`."""
     from . import shims
 
     repo_root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -367,8 +371,48 @@ def patch_reference(reference_root: str | None = None, fast_render: bool = True,
         seeded = True
     fused_loss = patch_loss_and_stats(gm.GaussianModel) if os.environ.get("GAA_FUSED_LOSS", "1") != "0" else []
     fused_adam = patch_optimizer(gm.GaussianModel, fgm.FlameGaussianModel) if os.environ.get("GAA_FUSED_ADAM", "1") != "0" else []
+    overlay = adopt_mesh_overlay() if os.environ.get("GAA_FUSED_OVERLAY", "1") != "0" else []
     return dict(shims=served, classes=[gm.GaussianModel, fgm.FlameGaussianModel, flame.FlameHead], render=did_render, pinned_cpus=pinned,
-                backward_seed=seeded, loss=fused_loss, optimizer=fused_adam)
+                backward_seed=seeded, loss=fused_loss, optimizer=fused_adam, overlay=overlay)
+
+
+def _overlay_render_mesh(self, verts, faces, RT, full_proj, image_size, background_color=[1.0, 1.0, 1.0], face_colors=None):
+    from . import mesh_renderer as M
+
+    return M.render_mesh(verts, faces, RT, full_proj, image_size, background_color, face_colors, lighting_type=self.lighting_type)
+
+
+def _overlay_render_from_camera(self, verts, faces, cam, background_color=[1.0, 1.0, 1.0], face_colors=None):
+    from . import mesh_renderer as M
+
+    return M.render_from_camera(verts, faces, cam, background_color, face_colors, lighting_type=self.lighting_type,
+                                use_opengl=self.use_opengl)
+
+
+def adopt_mesh_overlay(renderer_cls=None) -> list:
+    """The mesh overlay behind the zero-edit boundary: rebinds `render_mesh` and `render_from_camera` of the reference's
+    `mesh_renderer.NVDiffRenderer` (mesh_renderer/__init__.py:183-274; or of `renderer_cls`, any class with its `lighting_type` and
+    `use_opengl` attributes) to gaussianavatars_amd.mesh_renderer, which honours both attributes of the instance.  Same arguments, same dict
+    of four maps; forward only, device tensors only (a host tensor raises ValueError: there is no CPU path).  Without an importable
+    `mesh_renderer` module nothing is rebound.  Idempotent; undone by unpatch_classes; GAA_FUSED_OVERLAY=0 keeps patch_reference() from
+    calling it.  Returns the names rebound."""
+    cls = renderer_cls
+    if cls is None:
+        import importlib
+
+        try:
+            cls = importlib.import_module("mesh_renderer").NVDiffRenderer
+        except (ImportError, AttributeError):
+            return []
+    if cls.__dict__.get("_gaa_patched_overlay", False):
+        return []
+    done = []
+    for name, fn in (("render_mesh", _overlay_render_mesh), ("render_from_camera", _overlay_render_from_camera)):
+        _ORIG[(cls, name)] = cls.__dict__[name]
+        setattr(cls, name, fn)
+        done.append(f"{cls.__name__}.{name}")
+    cls._gaa_patched_overlay = True
+    return done
 
 
 def patch_optimizer(gaussian_model_cls, flame_gaussian_model_cls=None) -> list:

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define GMR_ABI_VERSION 1
+#define GMR_ABI_VERSION 2   /* 2: the shaded overlay of gmr_overlay.h, included below */
 #define GMR_OK 0
 #define GMR_E_ARG (-1)
 #define GMR_E_HIP (-2)
@@ -48,4 +48,7 @@ int gmr_antialias(int32_t B, int32_t V, int32_t F, int32_t H, int32_t W, int32_t
 #ifdef __cplusplus
 }
 #endif
+
+#include "gmr_overlay.h"   /* ABI 2: prepare, shade, resize / flip and compose, the rest of the overlay around the two calls above */
+
 #endif /* GMR_H */
