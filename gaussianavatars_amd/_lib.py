@@ -145,7 +145,7 @@ def profile_read(tags) -> dict:
 GSR_LIB_PATH = _lib_path("gsr", "GSR_LIB")
 
 GSR_OK = 0
-GSR_ABI_VERSION = 11
+GSR_ABI_VERSION = 12
 GSR_E_CAPACITY = 1
 GSR_COUNT_SLOTS = 128   # include/gsr.h: persistent instance-count slots of the deferred forwards
 
@@ -176,7 +176,7 @@ class GsrSettings(C.Structure):
 
 class GsrGeomLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in
-                ("depths", "grec", "cov3D", "rect", "tiles_touched", "clamped", "visible", "brec", "acc64", "acc", "total")]
+                ("depths", "grec", "cov3D", "rect", "tiles_touched", "clamped", "visible", "brec", "acc64", "acc", "shjac", "total")]
 
 
 class GsrBinningLayout(C.Structure):

@@ -276,6 +276,7 @@ int gsr_geom_layout(int32_t P, GsrGeomLayout* o)
     o->brec = off;          off = align_up(off + n * 48, A);
     o->acc64 = off;         off = align_up(off + n * GSR_ACC64_STRIDE * 8, A);
     o->acc = off;           off = align_up(off + n * GSR_ACC_STRIDE * 4, A);
+    o->shjac = off;         off = align_up(off + 9 * gsr::sh_jac_stride(n) * 4, A);
     o->total = off + A;
     return 0;
 }
@@ -486,6 +487,8 @@ static int forward_impl(const GsrSettings* settings, int32_t P, int32_t M, const
     pa.visible = (uint8_t*)(g + gl.visible);
     pa.acc = (float4*)(g + gl.acc);
     pa.acc64 = (float4*)(g + gl.acc64);
+    // d colour / d view direction for the backward: only where a backward that reads it can follow (cfg2 / cfg5-style frames pay nothing)
+    pa.shjac = gsr::sh_jac_stashed(settings->forward_only != 0, colors_precomp != nullptr, M) && shs ? (float*)(g + gl.shjac) : nullptr;
     pa.tile_count = tile_count;
     pa.units = (uint32_t*)(im + il.units);
     pa.rect_total = rect_total;
@@ -504,7 +507,8 @@ static int forward_impl(const GsrSettings* settings, int32_t P, int32_t M, const
     const int pblocks = (P + 255) / 256;
     if (pblocks > 0) {
         TIMED(GSR_K_PREPROCESS, stream);
-        hipLaunchKernelGGL(gsr::k_preprocess, dim3(pblocks), dim3(256), 0, stream, ds, pa);
+        auto* const pre_k = pa.shjac ? &gsr::k_preprocess<true> : &gsr::k_preprocess<false>;
+        hipLaunchKernelGGL(pre_k, dim3(pblocks), dim3(256), 0, stream, ds, pa);
         KERNEL_CHECK("k_preprocess", stream, dbg);
     }
 
@@ -928,6 +932,7 @@ static int backward_impl(const GsrSettings* settings, int32_t P, int32_t M, cons
     pa.acc64 = acc64;
     pa.gmax = gmax;
     pa.grec = (const float4*)(g + gl.grec);
+    pa.shjac = gsr::sh_jac_stashed(false, pre_col, M) ? (const float*)(g + gl.shjac) : nullptr;   // (the forward of this state was not forward_only: checked above)
     pa.use_precomp_cov = pre_cov ? 1 : 0;
     pa.use_precomp_color = pre_col ? 1 : 0;
     pa.dL_dmeans3D = dL_dmeans3D; pa.dL_dmeans2D = dL_dmeans2D; pa.dL_dsh = pre_col ? nullptr : dL_dsh; pa.dL_dsh_rest = shs_rest ? dL_dsh_rest : nullptr;

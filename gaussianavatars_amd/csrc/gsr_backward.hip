@@ -620,25 +620,19 @@ template __global__ void k_render_bwd_rp<4>(Settings, const uint32_t*, const uin
 
 // ------------------------------------------------------------------------------------------
 
-__global__ __launch_bounds__(GSR_PREBWD_ROWS) void k_preprocess_bwd(Settings s, PreBwdArgs a)
+// (amdgpu_waves_per_eu: four workgroups of 208 rows fill a CU's LDS -- gsr_device.h, GSR_PREBWD_ROWS -- which is four waves per SIMD and 128 VGPRs;
+//  left to itself the allocator takes 136 and the CU holds three)
+__global__ __launch_bounds__(GSR_PREBWD_ROWS) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_preprocess_bwd(Settings s, PreBwdArgs a)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int M = a.M;
-    // SH coefficients in, SH gradients out: both as one coalesced stream per workgroup through LDS
-    // (gsr_device.h); each thread reads its coefficient row and then overwrites it with the gradient row.
+    // SH gradients out as one coalesced stream per workgroup through LDS (gsr_device.h): each thread builds its gradient row in its LDS row.
+    // The coefficients themselves are not read on this path: the one term they enter, d colour / d view direction, comes from the forward
+    // (GsrGeomLayout.shjac, 36 bytes per splat instead of the 192-byte row).
     __shared__ float sh_lds[GSR_PREBWD_ROWS * GSR_SH_MAX_STRIDE];
-    const bool sh_staged = !a.use_precomp_color && a.dL_dsh != nullptr && M <= 16;
+    const bool sh_staged = a.dL_dsh != nullptr && a.shjac != nullptr;   // (gsr_api.hip: shjac is set under sh_jac_stashed, with colours from SH and M <= 16)
     const int first = blockIdx.x * GSR_PREBWD_ROWS, rows = min(GSR_PREBWD_ROWS, a.P - first);
     const int sh_stride = sh_row_stride(M);
-    if (sh_staged) {
-        if (a.shs_rest) {   // the model's two leaf tensors: DC (P,1,3) and rest (P,M-1,3)
-            sh_rows_load<GSR_PREBWD_ROWS>(sh_lds, a.shs, first, rows, 3, sh_stride, 0, (int)threadIdx.x);
-            sh_rows_load<GSR_PREBWD_ROWS>(sh_lds, a.shs_rest, first, rows, 3 * (M - 1), sh_stride, 3, (int)threadIdx.x);
-        } else {
-            sh_rows_load<GSR_PREBWD_ROWS>(sh_lds, a.shs, first, rows, 3 * M, sh_stride, 0, (int)threadIdx.x);
-        }
-        __syncthreads();
-    }
     if (i < a.P) {
     float dmean[3] = {0.f, 0.f, 0.f};
     float gcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -683,71 +677,32 @@ __global__ __launch_bounds__(GSR_PREBWD_ROWS) void k_preprocess_bwd(Settings s, 
         }
         const float* c6 = a.cov3D + 6 * i;
 
-        // ---- SH: coefficients and view direction (FIRST: its 48 coefficient registers are dead before the geometric chain below builds
-        // up its own -- 90 VGPRs instead of 130 with the two blocks the other way round) --------------------------------------------
+        // ---- SH: gradient rows and the view direction's share of dL/dmean (FIRST: on the M > 16 path its 48 coefficient registers are dead
+        // before the geometric chain below builds up its own -- 90 VGPRs instead of 130 with the two blocks the other way round) ---------
         if (!a.use_precomp_color) {
-            // the coefficient row is copied to registers first: in staged mode the gradient row overwrites it in LDS
-            float shr[48];
-            {
-                const float* row = sh_staged ? sh_lds + (int)threadIdx.x * sh_row_stride(M) : a.shs + (size_t)3 * M * i;
-#pragma unroll
-                for (int k = 0; k < 48; ++k) shr[k] = k < 3 * M ? row[k] : 0.f;
-            }
-            const float* sh = shr;
             const int deg = s.sh_degree;
             const float d0 = mx - s.campos[0], d1 = my - s.campos[1], d2 = mz - s.campos[2];
-            const float sum2 = d0 * d0 + d1 * d1 + d2 * d2;
-            const float inv_len = 1.0f / sqrtf(sum2);
-            const float x = d0 * inv_len, y = d1 * inv_len, z = d2 * inv_len;
+            float sum2, x, y, z;
+            sh_view_dir(d0, d1, d2, sum2, x, y, z);
             const uint32_t cl = a.clamped[i];
-            float ddir[3] = {0.f, 0.f, 0.f};
-            const float xx = x * x, yy = y * y, zz = z * z, xy_ = x * y, yz = y * z, xz = x * z;
+            const float g3[3] = {(cl & 1u) ? 0.f : gcol[0], (cl & 2u) ? 0.f : gcol[1], (cl & 4u) ? 0.f : gcol[2]};
+            float jac[9];
             const int ncoef = (deg + 1) * (deg + 1);
+            if (sh_staged) {   // the forward's nine floats; the gradient rows need the direction only
+                const float* jp = a.shjac + i;
+                const size_t js = sh_jac_stride((size_t)a.P);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float g = ((cl >> c) & 1u) ? 0.f : gcol[c];
-                float dxs = 0.f, dys = 0.f, dzs = 0.f;
-                gsh[0 + c] = kC0 * g;
-                if (deg > 0) {
-                    gsh[3 + c] = -kC1 * y * g;
-                    gsh[6 + c] = kC1 * z * g;
-                    gsh[9 + c] = -kC1 * x * g;
-                    dxs = -kC1 * sh[9 + c];
-                    dys = -kC1 * sh[3 + c];
-                    dzs = kC1 * sh[6 + c];
-                    if (deg > 1) {
-                        gsh[12 + c] = kC2_0 * xy_ * g;
-                        gsh[15 + c] = kC2_1 * yz * g;
-                        gsh[18 + c] = kC2_2 * (2.f * zz - xx - yy) * g;
-                        gsh[21 + c] = kC2_3 * xz * g;
-                        gsh[24 + c] = kC2_4 * (xx - yy) * g;
-                        dxs += kC2_0 * y * sh[12 + c] + kC2_2 * 2.f * -x * sh[18 + c] + kC2_3 * z * sh[21 + c] + kC2_4 * 2.f * x * sh[24 + c];
-                        dys += kC2_0 * x * sh[12 + c] + kC2_1 * z * sh[15 + c] + kC2_2 * 2.f * -y * sh[18 + c] + kC2_4 * 2.f * -y * sh[24 + c];
-                        dzs += kC2_1 * y * sh[15 + c] + kC2_2 * 2.f * 2.f * z * sh[18 + c] + kC2_3 * x * sh[21 + c];
-                        if (deg > 2) {
-                            gsh[27 + c] = kC3_0 * y * (3.f * xx - yy) * g;
-                            gsh[30 + c] = kC3_1 * xy_ * z * g;
-                            gsh[33 + c] = kC3_2 * y * (4.f * zz - xx - yy) * g;
-                            gsh[36 + c] = kC3_3 * z * (2.f * zz - 3.f * xx - 3.f * yy) * g;
-                            gsh[39 + c] = kC3_4 * x * (4.f * zz - xx - yy) * g;
-                            gsh[42 + c] = kC3_5 * z * (xx - yy) * g;
-                            gsh[45 + c] = kC3_6 * x * (xx - 3.f * yy) * g;
-                            dxs += kC3_0 * sh[27 + c] * 3.f * 2.f * xy_ + kC3_1 * sh[30 + c] * yz + kC3_2 * sh[33 + c] * -2.f * xy_ +
-                                   kC3_3 * sh[36 + c] * -3.f * 2.f * xz + kC3_4 * sh[39 + c] * (-3.f * xx + 4.f * zz - yy) +
-                                   kC3_5 * sh[42 + c] * 2.f * xz + kC3_6 * sh[45 + c] * 3.f * (xx - yy);
-                            dys += kC3_0 * sh[27 + c] * 3.f * (xx - yy) + kC3_1 * sh[30 + c] * xz +
-                                   kC3_2 * sh[33 + c] * (-3.f * yy + 4.f * zz - xx) + kC3_3 * sh[36 + c] * -3.f * 2.f * yz +
-                                   kC3_4 * sh[39 + c] * -2.f * xy_ + kC3_5 * sh[42 + c] * -2.f * yz + kC3_6 * sh[45 + c] * -3.f * 2.f * xy_;
-                            dzs += kC3_1 * sh[30 + c] * xy_ + kC3_2 * sh[33 + c] * 4.f * 2.f * yz +
-                                   kC3_3 * sh[36 + c] * 3.f * (2.f * zz - xx - yy) + kC3_4 * sh[39 + c] * 4.f * 2.f * xz +
-                                   kC3_5 * sh[42 + c] * (xx - yy);
-                        }
-                    }
-                }
-                ddir[0] += dxs * g;
-                ddir[1] += dys * g;
-                ddir[2] += dzs * g;
+                for (int k = 0; k < 9; ++k) jac[k] = jp[js * k];
+                sh_backward_terms<true, false>(deg, x, y, z, g3, [](int) { return 0.f; }, gsh, nullptr);
+            } else {           // M > 16: the coefficient row from global memory, the gradient row straight to it
+                float shr[48];
+                const float* row = a.shs + (size_t)3 * M * i;
+#pragma unroll
+                for (int k = 0; k < 48; ++k) shr[k] = k < 3 * M ? row[k] : 0.f;
+                sh_backward_terms<true, true>(deg, x, y, z, g3, [&](int k) { return shr[k]; }, gsh, jac);
             }
+            float ddir[3];
+            sh_jac_contract(jac, g3, ddir);
             for (int k = 3 * ncoef; k < 3 * M; ++k) gsh[k] = 0.f;   // coefficients above the active degree
             const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
             dmean[0] += ((sum2 - d0 * d0) * ddir[0] - d1 * d0 * ddir[1] - d2 * d0 * ddir[2]) * invsum32;

@@ -374,9 +374,9 @@ __device__ __forceinline__ void for_each_tile(int minx, int miny, int maxx, int 
 }
 
 // ---- SH rows staged through LDS -------------------------------------------------------------------
-// A splat's SH block is 3*M contiguous floats (192 B at degree 3).  Read or written per thread that is a
-// 192-byte stride between lanes; instead the workgroup moves its 256 rows as one contiguous, fully
-// coalesced float4 stream to/from LDS and every thread works on its own LDS row.  Row stride (3M)|1 is odd,
+// A splat's SH block is 3*M contiguous floats (192 B at degree 3).  Written per thread that is a
+// 192-byte stride between lanes; instead every thread builds its gradient row in LDS and the workgroup
+// moves its rows out as one contiguous, fully coalesced float4 stream.  Row stride (3M)|1 is odd,
 // so the per-thread dword accesses are bank-conflict free.
 #define GSR_SH_ROWS 256
 // k_preprocess_bwd: 208 splats per workgroup -- four workgroups' staged SH rows (208 x 49 floats each) fill the CU's 160 KB of LDS exactly: 16 waves
@@ -388,33 +388,7 @@ __device__ __forceinline__ void for_each_tile(int minx, int miny, int maxx, int 
 #define GSR_SH_MAX_STRIDE 49
 __device__ __forceinline__ int sh_row_stride(int M) { return (3 * M) | 1; }
 
-// copies `rows` source rows of width w into LDS columns [col0, col0+w) of rows laid out with `stride`
-template <int NT = GSR_SH_ROWS>
-__device__ __forceinline__ void sh_rows_load(float* __restrict__ lds, const float* __restrict__ src, int first, int rows, int w, int stride,
-                                             int col0, int tid)
-{
-    const int total = rows * w;
-    const float* base = src + (size_t)first * w;
-    if ((total & 3) == 0 && ((((size_t)first * w) & 3) == 0)) {
-        const float4* b4 = reinterpret_cast<const float4*>(base);
-        for (int f = tid * 4; f < total; f += NT * 4) {
-            const float4 v = b4[f >> 2];
-            int r = f / w, c = f - r * w;
-            const float e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                lds[r * stride + col0 + c] = e[k];
-                if (++c == w) { c = 0; ++r; }
-            }
-        }
-    } else {
-        for (int f = tid; f < total; f += NT) {
-            const int r = f / w, c = f - r * w;
-            lds[r * stride + col0 + c] = base[f];
-        }
-    }
-}
-
+// copies `rows` rows of width w from LDS columns [col0, col0+w) of rows laid out with `stride` to their contiguous place in `dst`
 template <int NT = GSR_SH_ROWS>
 __device__ __forceinline__ void sh_rows_store(const float* __restrict__ lds, float* __restrict__ dst, int first, int rows, int w, int stride,
                                               int col0, int tid)
@@ -438,6 +412,139 @@ __device__ __forceinline__ void sh_rows_store(const float* __restrict__ lds, flo
             const int r = f / w, c = f - r * w;
             base[f] = lds[r * stride + col0 + c];
         }
+    }
+}
+
+// ---- SH backward terms, shared by k_preprocess_bwd and k_preprocess ---------------------------------
+// The backward of the SH colour has two halves.  The gradient rows dL/dsh are the SH basis of the view direction times the clamped
+// dL/dcolor: they do not depend on the coefficients.  The coefficients enter one term only, the derivative of the colour with respect
+// to the view direction (3 x 3 per splat: d colour_c / d (x, y, z)), which the backward contracts with dL/dcolor on the way to dL/dmean.
+// k_preprocess has every coefficient in flight when it evaluates the colour, so it forms those nine floats there and parks them in the
+// geom state (GsrGeomLayout.shjac); k_preprocess_bwd then reads 36 bytes per splat instead of the 192-byte coefficient row.
+// Both kernels call the functions below, which fix the contraction mode themselves (the backward TU is built with -ffp-contract=fast, the
+// forward TUs with off): the stashed bytes are the ones the backward would compute.
+
+// whether a frame carries the stash: the forward writes it and the backward reads it under this one predicate
+__host__ __device__ __forceinline__ bool sh_jac_stashed(bool forward_only, bool precomp_color, int M) { return !forward_only && !precomp_color && M <= 16; }
+// plane stride of GsrGeomLayout.shjac (floats): the nine planes start on 256-byte boundaries
+__host__ __device__ __forceinline__ size_t sh_jac_stride(size_t P) { return (P + 63) & ~(size_t)63; }
+
+// the view direction as the backward normalises it: (d0, d1, d2) = mean - camera position
+__device__ __forceinline__ void sh_view_dir(float d0, float d1, float d2, float& sum2, float& x, float& y, float& z)
+{
+#pragma clang fp contract(fast)
+    sum2 = d0 * d0 + d1 * d1 + d2 * d2;
+    const float inv_len = 1.0f / sqrtf(sum2);
+    x = d0 * inv_len; y = d1 * inv_len; z = d2 * inv_len;
+}
+
+// products of the direction's components that the degree 2 and 3 terms share
+struct ShDir { float x, y, z, xx, yy, zz, xy, yz, xz; };
+__device__ __forceinline__ ShDir sh_dir_products(float x, float y, float z)
+{
+#pragma clang fp contract(fast)
+    ShDir d;
+    d.x = x; d.y = y; d.z = z;
+    d.xx = x * x; d.yy = y * y; d.zz = z * z; d.xy = x * y; d.yz = y * z; d.xz = x * z;
+    return d;
+}
+
+// One degree's terms of channel c.  GRAD: gsh[3 k + c] = basis_k(x, y, z) * g (g: the clamped dL/dcolor_c).  JAC: the degree's share of
+// (dxs, dys, dzs) = d colour_c / d (x, y, z) from the coefficients sh(3 k + c) -- degree 1 sets it, 2 and 3 add to it.  Per degree, so that
+// k_preprocess can form them in the block in which it has that degree's coefficients in registers for the colour.
+template <bool GRAD, bool JAC, class Sh>
+__device__ __forceinline__ void sh_terms_deg1(int c, const ShDir& d, float g, Sh sh, float* gsh, float& dxs, float& dys, float& dzs)
+{
+#pragma clang fp contract(fast)
+    const float x = d.x, y = d.y, z = d.z;
+    if (GRAD) {
+        gsh[3 + c] = -kC1 * y * g;
+        gsh[6 + c] = kC1 * z * g;
+        gsh[9 + c] = -kC1 * x * g;
+    }
+    if (JAC) {
+        dxs = -kC1 * sh(9 + c);
+        dys = -kC1 * sh(3 + c);
+        dzs = kC1 * sh(6 + c);
+    }
+}
+template <bool GRAD, bool JAC, class Sh>
+__device__ __forceinline__ void sh_terms_deg2(int c, const ShDir& d, float g, Sh sh, float* gsh, float& dxs, float& dys, float& dzs)
+{
+#pragma clang fp contract(fast)
+    const float x = d.x, y = d.y, z = d.z, xx = d.xx, yy = d.yy, zz = d.zz, xy_ = d.xy, yz = d.yz, xz = d.xz;
+    if (GRAD) {
+        gsh[12 + c] = kC2_0 * xy_ * g;
+        gsh[15 + c] = kC2_1 * yz * g;
+        gsh[18 + c] = kC2_2 * (2.f * zz - xx - yy) * g;
+        gsh[21 + c] = kC2_3 * xz * g;
+        gsh[24 + c] = kC2_4 * (xx - yy) * g;
+    }
+    if (JAC) {
+        dxs += kC2_0 * y * sh(12 + c) + kC2_2 * 2.f * -x * sh(18 + c) + kC2_3 * z * sh(21 + c) + kC2_4 * 2.f * x * sh(24 + c);
+        dys += kC2_0 * x * sh(12 + c) + kC2_1 * z * sh(15 + c) + kC2_2 * 2.f * -y * sh(18 + c) + kC2_4 * 2.f * -y * sh(24 + c);
+        dzs += kC2_1 * y * sh(15 + c) + kC2_2 * 2.f * 2.f * z * sh(18 + c) + kC2_3 * x * sh(21 + c);
+    }
+}
+template <bool GRAD, bool JAC, class Sh>
+__device__ __forceinline__ void sh_terms_deg3(int c, const ShDir& d, float g, Sh sh, float* gsh, float& dxs, float& dys, float& dzs)
+{
+#pragma clang fp contract(fast)
+    const float x = d.x, y = d.y, z = d.z, xx = d.xx, yy = d.yy, zz = d.zz, xy_ = d.xy, yz = d.yz, xz = d.xz;
+    if (GRAD) {
+        gsh[27 + c] = kC3_0 * y * (3.f * xx - yy) * g;
+        gsh[30 + c] = kC3_1 * xy_ * z * g;
+        gsh[33 + c] = kC3_2 * y * (4.f * zz - xx - yy) * g;
+        gsh[36 + c] = kC3_3 * z * (2.f * zz - 3.f * xx - 3.f * yy) * g;
+        gsh[39 + c] = kC3_4 * x * (4.f * zz - xx - yy) * g;
+        gsh[42 + c] = kC3_5 * z * (xx - yy) * g;
+        gsh[45 + c] = kC3_6 * x * (xx - 3.f * yy) * g;
+    }
+    if (JAC) {
+        dxs += kC3_0 * sh(27 + c) * 3.f * 2.f * xy_ + kC3_1 * sh(30 + c) * yz + kC3_2 * sh(33 + c) * -2.f * xy_ +
+               kC3_3 * sh(36 + c) * -3.f * 2.f * xz + kC3_4 * sh(39 + c) * (-3.f * xx + 4.f * zz - yy) +
+               kC3_5 * sh(42 + c) * 2.f * xz + kC3_6 * sh(45 + c) * 3.f * (xx - yy);
+        dys += kC3_0 * sh(27 + c) * 3.f * (xx - yy) + kC3_1 * sh(30 + c) * xz +
+               kC3_2 * sh(33 + c) * (-3.f * yy + 4.f * zz - xx) + kC3_3 * sh(36 + c) * -3.f * 2.f * yz +
+               kC3_4 * sh(39 + c) * -2.f * xy_ + kC3_5 * sh(42 + c) * -2.f * yz + kC3_6 * sh(45 + c) * -3.f * 2.f * xy_;
+        dzs += kC3_1 * sh(30 + c) * xy_ + kC3_2 * sh(33 + c) * 4.f * 2.f * yz +
+               kC3_3 * sh(36 + c) * 3.f * (2.f * zz - xx - yy) + kC3_4 * sh(39 + c) * 4.f * 2.f * xz +
+               kC3_5 * sh(42 + c) * (xx - yy);
+    }
+}
+
+// every degree up to `deg`, channel by channel (k_preprocess_bwd): jac[3 c + (0, 1, 2)] = d colour_c / d (x, y, z)
+template <bool GRAD, bool JAC, class Sh>
+__device__ __forceinline__ void sh_backward_terms(int deg, float x, float y, float z, const float* g3, Sh sh, float* gsh, float* jac)
+{
+#pragma clang fp contract(fast)
+    const ShDir d = sh_dir_products(x, y, z);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float g = GRAD ? g3[c] : 0.f;
+        float dxs = 0.f, dys = 0.f, dzs = 0.f;
+        if (GRAD) gsh[0 + c] = kC0 * g;
+        if (deg > 0) {
+            sh_terms_deg1<GRAD, JAC>(c, d, g, sh, gsh, dxs, dys, dzs);
+            if (deg > 1) {
+                sh_terms_deg2<GRAD, JAC>(c, d, g, sh, gsh, dxs, dys, dzs);
+                if (deg > 2) sh_terms_deg3<GRAD, JAC>(c, d, g, sh, gsh, dxs, dys, dzs);
+            }
+        }
+        if (JAC) { jac[3 * c + 0] = dxs; jac[3 * c + 1] = dys; jac[3 * c + 2] = dzs; }
+    }
+}
+
+// dL/d(view direction) = sum over the channels of (d colour_c / d dir) * (clamped dL/dcolor_c)
+__device__ __forceinline__ void sh_jac_contract(const float* jac, const float* g3, float* ddir)
+{
+#pragma clang fp contract(fast)
+    ddir[0] = ddir[1] = ddir[2] = 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        ddir[0] += jac[3 * c + 0] * g3[c];
+        ddir[1] += jac[3 * c + 1] * g3[c];
+        ddir[2] += jac[3 * c + 2] * g3[c];
     }
 }
 
@@ -518,6 +625,7 @@ struct PreprocessArgs {
     uint8_t* __restrict__ visible;        // [P] radii > 0
     float4* __restrict__ acc;             // [P][3] backward accumulators, zeroed here for visible splats
     float4* __restrict__ acc64;           // [P][5] the deterministic mode's (80 B per splat), zeroed instead when settings.deterministic
+    float* __restrict__ shjac;            // [9][sh_jac_stride(P)] d colour / d view direction of the visible splats, or null (sh_jac_stashed)
     uint32_t* __restrict__ tile_count;    // [tiles] zeroed here (the binning histogram of this frame)
     uint32_t* __restrict__ units;         // the GSR_UNIT_LISTS counters of GsrImageLayout.units are zeroed here (k_render<true> appends, k_render_bwd_rp consumes)
     unsigned long long* __restrict__ rect_total;   // zeroed here; k_count sums tiles_touched into it
@@ -551,6 +659,7 @@ struct PreBwdArgs {
     long long* __restrict__ acc64;        // deterministic mode: [P][10] the same sums in fixed point
     const uint32_t* __restrict__ gmax;    // deterministic mode: bits of max |dL/dpixel| (the fixed-point scale)
     const float4* __restrict__ grec;      // deterministic mode: the per-splat records (their fixed-point exponents)
+    const float* __restrict__ shjac;      // the forward's [9][sh_jac_stride(P)] d colour / d view direction, or null (sh_jac_stashed)
     int use_precomp_cov, use_precomp_color;
     float* __restrict__ dL_dmeans3D;
     float* __restrict__ dL_dmeans2D;      // (P,3)
@@ -565,6 +674,7 @@ struct PreBwdArgs {
     const float* __restrict__ opacities;  // bound entry: the opacity logits (sigmoid' for dL_dopacity)
 };
 
+template <bool STASH>   // STASH: writes GsrGeomLayout.shjac (a.shjac != nullptr)
 __global__ void k_preprocess(Settings s, PreprocessArgs a);
 __global__ void k_tile_scan(int tiles, const uint32_t* tile_count, uint32_t* tile_start, uint32_t* tile_cursor, uint2* ranges,
                             uint32_t* tile_order, unsigned long long* total_dev, unsigned long long* mailbox, unsigned long long seq, unsigned long long post_capacity);

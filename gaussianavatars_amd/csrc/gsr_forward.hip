@@ -27,6 +27,9 @@ namespace gsr {
 // k_preprocess
 // ------------------------------------------------------------------------------------------
 
+// STASH: the instance of frames whose backward reads GsrGeomLayout.shjac (gsr_device.h: sh_jac_stashed).  The other one -- forward_only frames,
+// precomputed colours -- carries none of its registers (62 VGPRs against 82).
+template <bool STASH>
 __global__ __launch_bounds__(256) void k_preprocess(Settings s, PreprocessArgs a)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -191,10 +194,26 @@ __global__ __launch_bounds__(256) void k_preprocess(Settings s, PreprocessArgs a
                         float res[3];
 #pragma unroll
                         for (int c = 0; c < 3; ++c) res[c] = kC0 * sh0[c];
+                        // The backward's one use of the coefficients -- d colour / d view direction, nine floats (GsrGeomLayout.shjac) -- is
+                        // formed here, degree by degree beside the colour, while that degree's coefficients are in registers, with the
+                        // backward's own expressions and its own normalisation of the direction (gsr_device.h: sh_terms_deg*).
+                        constexpr bool stash = STASH;
+                        const auto shf = [&](int k) { return sh[k]; };
+                        float jac[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                        ShDir bd = {};
+                        if (stash) {
+                            float sum2, bx, by, bz;
+                            sh_view_dir(dx, dy, dz, sum2, bx, by, bz);
+                            bd = sh_dir_products(bx, by, bz);
+                        }
                         if (deg > 0) {
 #pragma unroll
                             for (int c = 0; c < 3; ++c)
                                 res[c] = res[c] - kC1 * y * sh[3 + c] + kC1 * z * sh[6 + c] - kC1 * x * sh[9 + c];
+                            if (stash) {
+#pragma unroll
+                                for (int c = 0; c < 3; ++c) sh_terms_deg1<false, true>(c, bd, 0.f, shf, nullptr, jac[3 * c], jac[3 * c + 1], jac[3 * c + 2]);
+                            }
                             if (deg > 1) {
                                 const float xx = x * x, yy = y * y, zz = z * z;
                                 const float xy_ = x * y, yz = y * z, xz = x * z;
@@ -203,6 +222,10 @@ __global__ __launch_bounds__(256) void k_preprocess(Settings s, PreprocessArgs a
                                     res[c] = res[c] + kC2_0 * xy_ * sh[12 + c] + kC2_1 * yz * sh[15 + c] +
                                              kC2_2 * (2.0f * zz - xx - yy) * sh[18 + c] + kC2_3 * xz * sh[21 + c] +
                                              kC2_4 * (xx - yy) * sh[24 + c];
+                                if (stash) {
+#pragma unroll
+                                    for (int c = 0; c < 3; ++c) sh_terms_deg2<false, true>(c, bd, 0.f, shf, nullptr, jac[3 * c], jac[3 * c + 1], jac[3 * c + 2]);
+                                }
                                 if (deg > 2) {
 #pragma unroll
                                     for (int c = 0; c < 3; ++c)
@@ -211,6 +234,10 @@ __global__ __launch_bounds__(256) void k_preprocess(Settings s, PreprocessArgs a
                                                  kC3_3 * z * (2.0f * zz - 3.0f * xx - 3.0f * yy) * sh[36 + c] +
                                                  kC3_4 * x * (4.0f * zz - xx - yy) * sh[39 + c] +
                                                  kC3_5 * z * (xx - yy) * sh[42 + c] + kC3_6 * x * (xx - 3.0f * yy) * sh[45 + c];
+                                    if (stash) {
+#pragma unroll
+                                        for (int c = 0; c < 3; ++c) sh_terms_deg3<false, true>(c, bd, 0.f, shf, nullptr, jac[3 * c], jac[3 * c + 1], jac[3 * c + 2]);
+                                    }
                                 }
                             }
                         }
@@ -219,6 +246,12 @@ __global__ __launch_bounds__(256) void k_preprocess(Settings s, PreprocessArgs a
                             res[c] += 0.5f;
                             if (res[c] < 0.0f) clampbits |= (1u << c);
                             col[c] = sel_max(res[c], 0.0f);
+                        }
+                        if (stash) {   // plane-major: a wave stores (and the backward loads) 256 contiguous bytes per instruction; visible splats only
+                            float* jp = a.shjac + i;
+                            const size_t js = sh_jac_stride((size_t)a.P);
+#pragma unroll
+                            for (int k = 0; k < 9; ++k) jp[js * k] = jac[k];
                         }
                     }
                 }
@@ -389,6 +422,9 @@ __global__ __launch_bounds__(256) void k_preprocess(Settings s, PreprocessArgs a
         }
     }
 }
+
+template __global__ void k_preprocess<false>(Settings, PreprocessArgs);
+template __global__ void k_preprocess<true>(Settings, PreprocessArgs);
 
 // ------------------------------------------------------------------------------------------
 // k_count: instances per tile.  Each workgroup owns a contiguous chunk of splats and histograms

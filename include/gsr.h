@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 11
+#define GSR_ABI_VERSION 12
 #define GSR_BWD_SEGMENT 60        /* stream entries per backward segment (a multiple of both blend kernels' batches)  */
 #define GSR_BWD_SEGMENTS 10       /* segments per quadrant stream; the last one takes whatever is left                */
 #define GSR_UNIT_LISTS 64         /* fast blend: the backward's work units (quadrant, segment) are appended to this many lists (GsrImageLayout.units) */
@@ -79,7 +79,7 @@ typedef struct GsrSettings {
                                     The binning path of a call is GsrBinningLayout.path.                                       */
     int32_t forward_only;     /* !=0: no backward will follow this forward (inference, torch.no_grad): the forward skips zero-filling
                                  the backward's per-splat accumulators (48 B per visible splat) and writing what only the backward reads
-                                 (GsrGeomLayout.cov3D, clamped; rect on the rank path; round 4: the image state as well -- final_T,
+                                 (GsrGeomLayout.cov3D, clamped, shjac; rect on the rank path; round 4: the image state as well -- final_T,
                                  n_contrib, n_contrib_q, c_final and the blend checkpoints stay unwritten, only out_color leaves the
                                  blend); gsr_backward on such a state is an error                                          */
     int32_t deterministic;    /* !=0: bit-reproducible backward.  The blend backward then adds its per-(wave, splat) partial sums as 64-bit
@@ -147,6 +147,12 @@ typedef struct GsrGeomLayout {
                               dconic 3, dopacity 1, pad 3).  The forward zeroes the entries of visible splats and the
                               backward zeroes them again after consuming them, so a state is always ready for a
                               backward and no per-frame memset exists.                                 */
+    size_t shjac;          /* float  [9][S], S = P rounded up to 64 (ABI 12): the derivative of a splat's SH colour with respect to the unit
+                              view direction, plane 3 c + k = d colour_c / d (x, y, z)_k.  It is the only term of the backward that needs
+                              the SH coefficients; the forward has them in flight and writes these 36 bytes for every VISIBLE splat (rows of
+                              culled splats are never written and never read), so the backward does not fetch the 192-byte coefficient
+                              rows again.  Written only when a backward that reads it can follow: colours from SH, M <= 16, not
+                              forward_only.                                                                   */
     size_t total;
 } GsrGeomLayout;
 
