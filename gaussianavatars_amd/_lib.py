@@ -541,3 +541,44 @@ def gdc():
 gdc_error = partial(last_error, "gdc")
 gdc_profile_enable = partial(profile_enable, ("gdc",))
 gdc_profile_read = partial(profile_read, ("gdc",))
+
+
+# ------------------------------------------------------------------------------------------------
+# libgev_hip.so : evaluation and export (include/gev.h).  Loaded only by evaluate.py, at the first call on device tensors.
+# ------------------------------------------------------------------------------------------------
+#: tag -> LibSpec of the libraries added after MORE_LIBS was pinned to ["gdc"] in its turn (tests/test_densify_cpu.py, tests/test_knn_cpu.py);
+#: the third table works exactly like the other two: handle(), last_error() and the profile shims take its tags, and build() checks all three
+EVAL_LIBS = {}
+
+GEV_LIB_PATH = _lib_path("gev")
+GEV_ABI_VERSION = 1
+GEV_F32_PLANAR, GEV_U8_INTERLEAVED = 0, 1          # include/gev.h: layout of one image of a pair
+GEV_RAW, GEV_CLAMP, GEV_PNG8 = 0, 1, 2             # include/gev.h: load transform of a planar fp32 image
+GEV_PSNR_PER_CHANNEL, GEV_PSNR_PER_IMAGE = 0, 1    # include/gev.h: how an image's PSNR is formed from its planes
+
+_GEV_PAIR = [C.c_int32] * 4 + [_P, C.c_int32, _P, C.c_int32, C.c_int32]   # B, C, H, W, a, a_layout, b, b_layout, transform
+GEV_SYMBOLS = {
+    "gev_abi_version": (C.c_int, []),
+    "gev_last_error": (C.c_char_p, []),
+    "gev_partial_floats": (C.c_int64, [C.c_int32] * 4),
+    "gev_pair_stats": (C.c_int, _GEV_PAIR + [_P, _P, _P]),
+    "gev_accumulate": (C.c_int, _GEV_PAIR + [C.c_int32, _P, _P, _P, C.c_int32, _P, _P]),
+    "gev_to_u8": (C.c_int, [C.c_int32] * 4 + [_P, _P, _P, _P, _P]),
+    **_profile_symbols("gev"),
+}
+
+EVAL_LIBS["gev"] = LibSpec("gev", GEV_LIB_PATH, GEV_SYMBOLS, GEV_ABI_VERSION)
+_gev = None
+
+
+def gev():
+    """The evaluation library; raises (never falls back) when it is not built."""
+    global _gev
+    if _gev is None:
+        _gev = _load(EVAL_LIBS["gev"])
+    return _gev
+
+
+gev_error = partial(last_error, "gev")
+gev_profile_enable = partial(profile_enable, ("gev",))
+gev_profile_read = partial(profile_read, ("gev",))

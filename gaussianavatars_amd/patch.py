@@ -14,6 +14,7 @@ What is rebound (attribute names, lazy initialisation and autograd connectivity 
     gaussian_renderer.render (optional)          gaussian_renderer/__init__.py:19-101   -> the mirror with the split-SH / leaf fast paths
     GaussianModel.densify_and_prune              scene/gaussian_model.py:501-515        -> gdc_plan + gdc_emit (densify.py; GAA_FUSED_DENSIFY=0 opts out)
     NVDiffRenderer.render_mesh / render_from_camera   mesh_renderer/__init__.py:183-274   -> mesh_renderer.py (include/gmr_overlay.h; GAA_FUSED_OVERLAY=0 opts out)
+    utils.image_utils.psnr                       utils/image_utils.py:18-20              -> evaluate.psnr (include/gev.h; GAA_FUSED_EVAL=0 opts out)
 
 `patch_classes` works on any class pair with the reference's attribute names; the repository's own mirror classes
 (gaussianavatars_amd/gaussian_model.py) are written in composed torch like the reference and go through the very same
@@ -307,7 +308,7 @@ def unpatch_classes(*classes) -> None:
             del _ORIG[(cls, name)]
     for cls in classes:
         for flag in ("_gaa_patched", "_gaa_patched_flame", "_gaa_patched_head", "_gaa_patched_base", "_gaa_patched_stats", "_gaa_patched_optimizer",
-                     "_gaa_patched_overlay"):
+                     "_gaa_patched_overlay", "_gaa_patched_eval", "_gaa_orig_psnr"):
             if flag in cls.__dict__:
                 delattr(cls, flag)
         if isinstance(cls.__dict__.get("get_features_split"), property) and cls.__dict__["get_features_split"].fget is _get_features_split:
@@ -333,8 +334,10 @@ def patch_reference(reference_root: str | None = None, fast_render: bool = True,
        train.py:209's `gaussians.optimizer.step()` is one launch of include/gop.h.
     8. (GAA_FUSED_OVERLAY=0 opts out) adopt_mesh_overlay: `NVDiffRenderer.render_mesh` / `render_from_camera` (render.py --render_mesh, the
        viewers' show_mesh) run on mesh_renderer.py: six launches instead of the composed torch around rasterize and antialias.
+    9. (GAA_FUSED_EVAL=0 opts out) adopt_evaluation: `utils.image_utils.psnr` (train.py:287, metrics.py:73) -> evaluate.psnr, two launches of
+       include/gev.h.
     Returns {'shims': [...], 'classes': [...], 'render': bool, 'pinned_cpus': [...] | None, 'backward_seed': bool, 'loss': [...],
-    'optimizer': [...], 'overlay': [...]}.  Call it before the entry script imports `render`."""
+    'optimizer': [...], 'overlay': [...], 'evaluation': [...]}.  Call it before the entry script imports `render`."""
     from . import shims
 
     repo_root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -372,8 +375,44 @@ def patch_reference(reference_root: str | None = None, fast_render: bool = True,
     fused_loss = patch_loss_and_stats(gm.GaussianModel) if os.environ.get("GAA_FUSED_LOSS", "1") != "0" else []
     fused_adam = patch_optimizer(gm.GaussianModel, fgm.FlameGaussianModel) if os.environ.get("GAA_FUSED_ADAM", "1") != "0" else []
     overlay = adopt_mesh_overlay() if os.environ.get("GAA_FUSED_OVERLAY", "1") != "0" else []
+    evaluation = adopt_evaluation() if os.environ.get("GAA_FUSED_EVAL", "1") != "0" else []
     return dict(shims=served, classes=[gm.GaussianModel, fgm.FlameGaussianModel, flame.FlameHead], render=did_render, pinned_cpus=pinned,
-                backward_seed=seeded, loss=fused_loss, optimizer=fused_adam, overlay=overlay)
+                backward_seed=seeded, loss=fused_loss, optimizer=fused_adam, overlay=overlay, evaluation=evaluation)
+
+
+def adopt_evaluation(image_utils=None) -> list:
+    """Evaluation behind the zero-edit boundary: rebinds `utils.image_utils.psnr` (utils/image_utils.py:18-20; or that of `image_utils`, any
+    module with a `psnr`) to evaluate.psnr BEFORE the entry script imports it (train.py:23, metrics.py:21): a device pair of fp32 images of one
+    shape, 3-D or 4-D, takes two launches of include/gev.h instead of about six; anything else -- host tensors, other dtypes, other ranks,
+    shapes that broadcast -- keeps the reference's own function, kept on the module as `_gaa_orig_psnr`.  Without an importable
+    `utils.image_utils` nothing is rebound.  Idempotent; undone by unpatch_classes(module); GAA_FUSED_EVAL=0 keeps patch_reference() from
+    calling it.  Returns the names rebound.  (l1_loss / ssim keep their paired rebinding of patch_loss_and_stats.)"""
+    iu = image_utils
+    if iu is None:
+        import importlib
+
+        try:
+            iu = importlib.import_module("utils.image_utils")
+        except ImportError:
+            return []
+    if getattr(iu, "_gaa_patched_eval", False) or not hasattr(iu, "psnr"):
+        return []
+    from . import evaluate as E
+
+    orig = iu.psnr
+    _ORIG[(iu, "psnr")] = orig
+
+    def psnr(img1, img2):
+        if not (isinstance(img1, torch.Tensor) and img1.is_cuda and img1.dtype is torch.float32 and img1.dim() in (3, 4)
+                and isinstance(img2, torch.Tensor) and img2.is_cuda and img2.dtype is torch.float32 and img1.shape == img2.shape):
+            return orig(img1, img2)
+        return E.psnr(img1, img2)
+
+    psnr.__doc__ = E.psnr.__doc__
+    iu._gaa_orig_psnr = orig
+    iu.psnr = psnr
+    iu._gaa_patched_eval = True
+    return [f"{getattr(iu, '__name__', 'utils.image_utils')}.psnr"]
 
 
 def _overlay_render_mesh(self, verts, faces, RT, full_proj, image_size, background_color=[1.0, 1.0, 1.0], face_colors=None):
