@@ -582,3 +582,45 @@ def gev():
 gev_error = partial(last_error, "gev")
 gev_profile_enable = partial(profile_enable, ("gev",))
 gev_profile_read = partial(profile_read, ("gev",))
+
+
+# ------------------------------------------------------------------------------------------------
+# libgfs_hip.so : the resident frame store (include/gfs.h).  Loaded only by frames.py, at the first ingest or fetch on device tensors.
+# ------------------------------------------------------------------------------------------------
+#: tag -> LibSpec of the libraries added after EVAL_LIBS was pinned to ["gev"] in its turn (tests/test_eval_cpu.py); the fourth table works
+#: exactly like the other three: handle(), last_error() and the profile shims take its tags, and build() checks all four
+FRAME_LIBS = {}
+
+GFS_LIB_PATH = _lib_path("gfs")
+GFS_ABI_VERSION = 1
+GFS_E_RANGE = -3               # include/gfs.h: a host index outside the store
+GFS_TABLE_ENTRIES = 256        # include/gfs.h: floats of the byte-to-float table
+GFS_MAX_BATCH = 65535          # include/gfs.h: frames per gfs_fetch_batch / gfs_compose launch
+GFS_FLAG_RANGE = 1             # include/gfs.h: bit of the device flag word
+
+GFS_SYMBOLS = {
+    "gfs_abi_version": (C.c_int, []),
+    "gfs_last_error": (C.c_char_p, []),
+    "gfs_frame_stride": (C.c_int64, [C.c_int32, C.c_int32]),
+    "gfs_compose": (C.c_int, [C.c_int32, C.c_int32, _P, C.POINTER(C.c_double), _P, C.c_int64, C.c_int64, C.c_int32, _P]),
+    "gfs_fetch": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int64, C.c_int64, _P, _P, _P]),
+    "gfs_fetch_indexed": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P, _P, _P]),
+    "gfs_fetch_batch": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, _P, _P, _P]),
+    **_profile_symbols("gfs"),
+}
+
+FRAME_LIBS["gfs"] = LibSpec("gfs", GFS_LIB_PATH, GFS_SYMBOLS, GFS_ABI_VERSION)
+_gfs = None
+
+
+def gfs():
+    """The frame-store library; raises (never falls back) when it is not built."""
+    global _gfs
+    if _gfs is None:
+        _gfs = _load(FRAME_LIBS["gfs"])
+    return _gfs
+
+
+gfs_error = partial(last_error, "gfs")
+gfs_profile_enable = partial(profile_enable, ("gfs",))
+gfs_profile_read = partial(profile_read, ("gfs",))

@@ -8,6 +8,7 @@ import math
 
 import torch
 
+from . import frames as _frames
 from . import patch as _patch   # (module level: a function-level `from . import x` costs ~1.5 us per call on a step whose host side is counted in microseconds)
 from .loss import l1_loss as _l1_loss
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_bound, rasterize_leaves
@@ -65,6 +66,17 @@ def _dev(t, device):
     return torch.as_tensor(t, device=device)
 
 
+def _camera_on(camera, device):
+    """(world_view_transform, full_proj_transform, camera_center) of `camera` on `device`.  A camera a ResidentCameraDataset tagged `_gaa_frame`, whose
+    frame store this process holds on `device`, takes three views into the store's camera block (frames.py: the same bits, uploaded once at ingest);
+    every other camera uploads its three host tensors, as before."""
+    if getattr(camera, "_gaa_frame", None) is not None:
+        hit = _frames.resident_camera(camera, device)
+        if hit is not None:
+            return hit
+    return (_dev(camera.world_view_transform, device), _dev(camera.full_proj_transform, device), _dev(camera.camera_center, device))
+
+
 def _bound_fast_path(pc, pipe, override_color) -> bool:
     """A patched mesh-bound model rendered the default way: the rasterizer's bound entry takes the model's leaves and per-face frames
     and evaluates get_xyz / get_scaling / get_rotation / get_opacity inside its first kernel -- one autograd
@@ -85,12 +97,13 @@ def _render_bound(viewpoint_camera, pc, pipe, bg_color, scaling_modifier):
         pc.select_mesh_by_timestep(0)
     device = pc._xyz.device
     screenspace_points = _screenspace_leaf(pc._xyz)
+    viewmatrix, projmatrix, campos = _camera_on(viewpoint_camera, device)
     raster_settings = GaussianRasterizationSettings(
         image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
         tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5), bg=bg_color,
-        scale_modifier=scaling_modifier, viewmatrix=_dev(viewpoint_camera.world_view_transform, device),
-        projmatrix=_dev(viewpoint_camera.full_proj_transform, device), sh_degree=pc.active_sh_degree,
-        campos=_dev(viewpoint_camera.camera_center, device), prefiltered=False, debug=pipe.debug)
+        scale_modifier=scaling_modifier, viewmatrix=viewmatrix,
+        projmatrix=projmatrix, sh_degree=pc.active_sh_degree,
+        campos=campos, prefiltered=False, debug=pipe.debug)
     dc, rest = pc.get_features_split
     if unbound:
         image, radii, visible = rasterize_leaves(pc._xyz, screenspace_points, dc, rest, pc._opacity, pc._scaling, pc._rotation, raster_settings)
@@ -109,6 +122,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     screenspace_points = _screenspace_leaf(xyz)
     tanfovx = math.tan(viewpoint_camera.FoVx * 0.5)
     tanfovy = math.tan(viewpoint_camera.FoVy * 0.5)
+    viewmatrix, projmatrix, campos = _camera_on(viewpoint_camera, device)
     raster_settings = GaussianRasterizationSettings(
         image_height=int(viewpoint_camera.image_height),
         image_width=int(viewpoint_camera.image_width),
@@ -116,10 +130,10 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         tanfovy=tanfovy,
         bg=bg_color,
         scale_modifier=scaling_modifier,
-        viewmatrix=_dev(viewpoint_camera.world_view_transform, device),
-        projmatrix=_dev(viewpoint_camera.full_proj_transform, device),
+        viewmatrix=viewmatrix,
+        projmatrix=projmatrix,
         sh_degree=pc.active_sh_degree,
-        campos=_dev(viewpoint_camera.camera_center, device),
+        campos=campos,
         prefiltered=False,
         debug=pipe.debug,
     )

@@ -15,6 +15,7 @@ What is rebound (attribute names, lazy initialisation and autograd connectivity 
     GaussianModel.densify_and_prune              scene/gaussian_model.py:501-515        -> gdc_plan + gdc_emit (densify.py; GAA_FUSED_DENSIFY=0 opts out)
     NVDiffRenderer.render_mesh / render_from_camera   mesh_renderer/__init__.py:183-274   -> mesh_renderer.py (include/gmr_overlay.h; GAA_FUSED_OVERLAY=0 opts out)
     utils.image_utils.psnr                       utils/image_utils.py:18-20              -> evaluate.psnr (include/gev.h; GAA_FUSED_EVAL=0 opts out)
+    scene.Scene.getTrainCameras                  scene/__init__.py:159-160               -> frames.ResidentCameraDataset over a FrameStore (include/gfs.h; GAA_FRAME_STORE=0 opts out)
 
 `patch_classes` works on any class pair with the reference's attribute names; the repository's own mirror classes
 (gaussianavatars_amd/gaussian_model.py) are written in composed torch like the reference and go through the very same
@@ -308,7 +309,7 @@ def unpatch_classes(*classes) -> None:
             del _ORIG[(cls, name)]
     for cls in classes:
         for flag in ("_gaa_patched", "_gaa_patched_flame", "_gaa_patched_head", "_gaa_patched_base", "_gaa_patched_stats", "_gaa_patched_optimizer",
-                     "_gaa_patched_overlay", "_gaa_patched_eval", "_gaa_orig_psnr"):
+                     "_gaa_patched_overlay", "_gaa_patched_eval", "_gaa_orig_psnr", "_gaa_patched_frames"):
             if flag in cls.__dict__:
                 delattr(cls, flag)
         if isinstance(cls.__dict__.get("get_features_split"), property) and cls.__dict__["get_features_split"].fget is _get_features_split:
@@ -336,8 +337,11 @@ def patch_reference(reference_root: str | None = None, fast_render: bool = True,
        viewers' show_mesh) run on mesh_renderer.py: six launches instead of the composed torch around rasterize and antialias.
     9. (GAA_FUSED_EVAL=0 opts out) adopt_evaluation: `utils.image_utils.psnr` (train.py:287, metrics.py:73) -> evaluate.psnr, two launches of
        include/gev.h.
+    10. (GAA_FRAME_STORE=0 opts out) adopt_frame_store: `scene.Scene.getTrainCameras` returns a frames.ResidentCameraDataset: the ground truth and
+       the cameras of the training frames stay in HBM (include/gfs.h), train.py:55's DataLoader workers pass placeholders on and train.py:128's
+       `.cuda()` is one launch instead of a 5.3 MB pageable upload.
     Returns {'shims': [...], 'classes': [...], 'render': bool, 'pinned_cpus': [...] | None, 'backward_seed': bool, 'loss': [...],
-    'optimizer': [...], 'overlay': [...], 'evaluation': [...]}.  Call it before the entry script imports `render`."""
+    'optimizer': [...], 'overlay': [...], 'evaluation': [...], 'frames': [...]}.  Call it before the entry script imports `render`."""
     from . import shims
 
     repo_root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -376,8 +380,59 @@ def patch_reference(reference_root: str | None = None, fast_render: bool = True,
     fused_adam = patch_optimizer(gm.GaussianModel, fgm.FlameGaussianModel) if os.environ.get("GAA_FUSED_ADAM", "1") != "0" else []
     overlay = adopt_mesh_overlay() if os.environ.get("GAA_FUSED_OVERLAY", "1") != "0" else []
     evaluation = adopt_evaluation() if os.environ.get("GAA_FUSED_EVAL", "1") != "0" else []
+    frames = adopt_frame_store() if os.environ.get("GAA_FRAME_STORE", "1") != "0" else []
     return dict(shims=served, classes=[gm.GaussianModel, fgm.FlameGaussianModel, flame.FlameHead], render=did_render, pinned_cpus=pinned,
-                backward_seed=seeded, loss=fused_loss, optimizer=fused_adam, overlay=overlay, evaluation=evaluation)
+                backward_seed=seeded, loss=fused_loss, optimizer=fused_adam, overlay=overlay, evaluation=evaluation, frames=frames)
+
+
+def _make_resident_getter(orig, name, device):
+    def getter(self, scale=1.0):
+        from . import frames as FR
+
+        dataset = orig(self, scale)
+        if not FR.fused_default() or not hasattr(dataset, "cameras"):
+            return dataset
+        cache = self.__dict__.setdefault("_gaa_frame_stores", {})
+        hit = cache.get((name, scale))
+        if hit is None or hit[0] is not dataset.cameras:   # (built on the first call, in the process that makes it: before train.py:55 forks its workers)
+            dev = device if device is not None else torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+            hit = cache[(name, scale)] = (dataset.cameras, FR.FrameStore.from_cameras(dataset.cameras, dev))
+        return FR.ResidentCameraDataset(dataset.cameras, hit[1], fallback=dataset)
+
+    getter.__name__ = name
+    getter.__doc__ = orig.__doc__
+    return getter
+
+
+def adopt_frame_store(scene_cls=None, device=None) -> list:
+    """The training frames behind the zero-edit boundary: wraps `getTrainCameras` of the reference's `scene.Scene` (scene/__init__.py:159-160; or of
+    `scene_cls`, any class whose getters return a dataset with a `cameras` list) so that it returns a frames.ResidentCameraDataset over a
+    frames.FrameStore on `device` (default: the current GPU; the host without one).  The store is built at the first call -- train.py:55, in the
+    main process, before the DataLoader forks its workers -- and kept on the Scene object, one per (getter, scale); train.py and its DataLoader
+    line stay unedited.  Frames the store does not hold (budget, a size other than the file's) run the reference's own `__getitem__`.
+    `getValCameras` / `getTestCameras` are wrapped only under GAA_FRAME_STORE_EVAL=1.  GAA_FRAME_STORE=0 (read at every call of the getter, and
+    by patch_reference()) gives the reference's dataset.  Without an importable `scene.Scene` nothing is rebound.  Idempotent; undone by
+    unpatch_classes.  Returns the names rebound."""
+    cls = scene_cls
+    if cls is None:
+        import importlib
+
+        try:
+            cls = importlib.import_module("scene").Scene
+        except (ImportError, AttributeError):
+            return []
+    if cls.__dict__.get("_gaa_patched_frames", False):
+        return []
+    names = ["getTrainCameras"] + (["getValCameras", "getTestCameras"] if os.environ.get("GAA_FRAME_STORE_EVAL", "0") == "1" else [])
+    done = []
+    for name in names:
+        if name not in cls.__dict__:
+            continue
+        _ORIG[(cls, name)] = cls.__dict__[name]
+        setattr(cls, name, _make_resident_getter(cls.__dict__[name], name, device))
+        done.append(f"{cls.__name__}.{name}")
+    cls._gaa_patched_frames = True
+    return done
 
 
 def adopt_evaluation(image_utils=None) -> list:
