@@ -60,7 +60,7 @@ __device__ __forceinline__ void load_halo(float (*dst)[HXS], const float* __rest
     }
 }
 
-__global__ __launch_bounds__(256) void k_l1_ssim_fwd(int H, int W, const float* __restrict__ img1, const float* __restrict__ img2,
+__global__ __launch_bounds__(256, 6) void k_l1_ssim_fwd(int H, int W, const float* __restrict__ img1, const float* __restrict__ img2,
                                                       Window win, float* __restrict__ maps, size_t map_stride,
                                                       float2* __restrict__ partial)
 {
@@ -118,19 +118,23 @@ __global__ __launch_bounds__(256) void k_l1_ssim_fwd(int H, int W, const float* 
         }
         const int ty = ty0 + j, px = x0 + tx, py = y0 + ty;
         if (px < W && py < H) {
+            // (no contraction from here on, and the map as the product of two quotients: for an identical pair A == C and B == D bit for
+            //  bit, so the map is exactly 1, d m / d mu1 exactly 0 and d m / d E[xy] exactly -2 d m / d E[x^2], and the backward returns the
+            //  zero gradient the reference returns.  Contracted, 2 x cb + y cc left the rounding of one product behind: 1e-8 at one pixel.)
+#pragma clang fp contract(off)
             const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
             const float s1 = e11 - mu1_sq, s2 = e22 - mu2_sq, s12 = e12 - mu12;
             const float A = 2.f * mu12 + SSIM_C1, Bv = 2.f * s12 + SSIM_C2;
             const float Cv = mu1_sq + mu2_sq + SSIM_C1, D = s1 + s2 + SSIM_C2;
-            const float inv = 1.f / (Cv * D);
-            const float m = A * Bv * inv;
+            const float inv = 1.f / (Cv * D), rD = 1.f / D;
+            const float qa = A / Cv, m = qa * (Bv / D);
             ss += m;
             l1 += fabsf(sx[ty + RAD][tx + RAD] - sy[ty + RAD][tx + RAD]);
             if (maps) {
                 const size_t o = poff + (size_t)py * W + px;
                 maps[o] = (2.f * mu2 * (Bv - A) - m * 2.f * mu1 * (D - Cv)) * inv;   // d m / d mu1  (E[x^2], E[xy] held fixed)
-                maps[o + map_stride] = -m / D;                                       // d m / d E[x^2]
-                maps[o + 2 * map_stride] = 2.f * A * inv;                            // d m / d E[xy]
+                maps[o + map_stride] = -(m * rD);                                    // d m / d E[x^2]
+                maps[o + 2 * map_stride] = (2.f * qa) * rD;                          // d m / d E[xy]
             }
         }
     }
@@ -219,6 +223,7 @@ __global__ __launch_bounds__(256) void k_l1_ssim_bwd(int C, int H, int W, const 
         }
         const int px = x0 + tx, py = y0 + ty0 + j;
         if (px < W && py < H) {
+#pragma clang fp contract(off)   // (2 x cb and y cc rounded alike: they cancel exactly where cc == -2 cb, see k_l1_ssim_fwd)
             const size_t o = poff + (size_t)py * W + px;
             const float x = img1[o], y = img2[o];
             const float df = x - y;
@@ -233,10 +238,18 @@ __device__ __forceinline__ float sgn_scaled(float d, float g) { return d > 0.f ?
 // GRAD: also d_a <- gs * sign(a - b), the gradient for an upstream gradient of exactly 1 (gs = the forward's mean scale): a backward seeded
 // with the constant 1 (loss.backward() on the loss itself) then has nothing left to launch
 // FUSED (round 6): the reduction over the workgroups without a second launch and without a fence.  Every workgroup adds its partial, as 2^-30
-// fixed point, and a 1 in the top byte to ONE 64-bit word with ONE returning atomic: the atomic is the only thing the workgroups share, so the one
-// that reads back (grid - 1) arrivals holds every other partial in the value it got -- it writes the loss and leaves the word zero for the
-// stream's next call.  Integer adds commute: the same bits whatever order the workgroups arrive in.  (Rounds 2 - 3 measured a ticket + fence +
-// re-read of the partials at the price of the launch it replaced; here nothing is re-read.)  At most 255 workgroups; |a - b| sums below 2^26.
+// fixed point in bits 8 .. 62, and a 1 in the low byte to ONE 64-bit word with ONE returning atomic: the atomic is the only thing the workgroups
+// share, so the one that reads back (grid - 1) arrivals holds every other partial in the value it got -- it writes the loss and leaves the word
+// zero for the stream's next call.  Integer adds commute: the same bits whatever order the workgroups arrive in.  (Rounds 2 - 3 measured a
+// ticket + fence + re-read of the partials at the price of the launch it replaced; here nothing is re-read.)  At most 255 workgroups.
+// A partial takes that road only while it is below 2^17: 255 of them stay below 2^55, so the field never carries into bit 63 and the count, in
+// the LOW byte, is never touched by a sum -- the last arriver is always found and always resets.  Anything else (!(tot < 2^17): a large
+// partial, inf, NaN) goes to the stream's two side words first and sets bit 63 (an OR with release order, then the arrival add on the same
+// address): word[1] takes partials below 2^26 as the same fixed point (255 of them fit 64 bits: the integer total, and with it the loss, is the
+// bits one word would have given whenever the total fits 56 bits), word[2] takes the rest as a double (inf and NaN stay what they are).  The last
+// arriver reads the side words only when it sees bit 63, so the usual image costs what it did.
+constexpr float kL1Small = 131072.f, kL1Mid = 67108864.f;   // 2^17, 2^26
+constexpr unsigned long long kL1Aside = 1ull << 63;
 template <bool GRAD, bool FUSED>
 __global__ __launch_bounds__(1024) void k_l1_fwd(long long n, const float* __restrict__ a, const float* __restrict__ b, float2* __restrict__ partial,
                                                   float gs, float* __restrict__ d_a, unsigned long long* __restrict__ word, float* __restrict__ sum)
@@ -265,11 +278,26 @@ __global__ __launch_bounds__(1024) void k_l1_fwd(long long n, const float* __res
         float tot = (red[0] + red[1]) + (red[2] + red[3]);
         for (int w = 4; w < (nt >> 6); w += 4) tot += (red[w] + red[w + 1]) + (red[w + 2] + red[w + 3]);
         if constexpr (FUSED) {
-            const unsigned long long mine = (unsigned long long)((double)tot * 1073741824.0 + 0.5) & 0x00FFFFFFFFFFFFFFull;
-            const unsigned long long old = atomicAdd(word, mine + (1ull << 56));
-            if ((old >> 56) == (unsigned long long)(gridDim.x - 1)) {
-                const unsigned long long all = (old & 0x00FFFFFFFFFFFFFFull) + mine;
-                *sum = gs * (float)((double)all * (1.0 / 1073741824.0));
+            unsigned long long mine = 0;
+            if (tot < kL1Small) {
+                mine = (unsigned long long)((double)tot * 1073741824.0 + 0.5);
+            } else {   // (NaN arrives here too)
+                if (tot < kL1Mid) __hip_atomic_fetch_add(word + 1, (unsigned long long)((double)tot * 1073741824.0 + 0.5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                else __hip_atomic_fetch_add((double*)(word + 2), (double)tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_or(word, kL1Aside, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            const unsigned long long old = __hip_atomic_fetch_add(word, (mine << 8) + 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if ((old & 0xFFull) == (unsigned long long)(gridDim.x - 1)) {
+                unsigned long long all = ((old & ~kL1Aside) >> 8) + mine;
+                double rest = 0.0;
+                if (old & kL1Aside) {
+                    all += __hip_atomic_load(word + 1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+                    rest = __hip_atomic_load((double*)(word + 2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(word + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store((double*)(word + 2), 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                const double fixed = (double)all * (1.0 / 1073741824.0);
+                *sum = gs * (float)(fixed + rest);   // (rest == 0: the bits of `fixed`)
                 __hip_atomic_store(word, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (the next call on this stream starts from zero)
             }
         } else {
@@ -410,10 +438,11 @@ int gls_l1_ssim_backward_split(int32_t B, int32_t C, int32_t H, int32_t W, const
     return l1_ssim_backward_impl(B, C, H, W, img1, img2, maps, g_l1, g_ssim, g_stride, scale, d_img1, stream_);
 }
 
-// one accumulator word of the fused L1 forward per stream (calls on a stream are ordered, concurrent streams never share a word)
+// the accumulator word of the fused L1 forward and its two side words, one group of kL1Group per stream (calls on a stream are ordered,
+// concurrent streams never share a group)
 static unsigned long long* l1_word_for(hipStream_t stream)
 {
-    constexpr int kWords = 64;
+    constexpr int kWords = 64, kL1Group = 4;
     static std::mutex mu;
     static std::vector<hipStream_t> owners;
     static std::vector<int> owner_dev;                  // (the table is keyed by (device, stream))
@@ -428,8 +457,8 @@ static unsigned long long* l1_word_for(hipStream_t stream)
     if (!b) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return nullptr;   // (no allocation inside a capture: the two-launch form)
-        if (hipMalloc((void**)&b, kWords * sizeof(unsigned long long)) != hipSuccess) return nullptr;
-        if (hipMemset(b, 0, kWords * sizeof(unsigned long long)) != hipSuccess) return nullptr;
+        if (hipMalloc((void**)&b, kWords * kL1Group * sizeof(unsigned long long)) != hipSuccess) return nullptr;
+        if (hipMemset(b, 0, kWords * kL1Group * sizeof(unsigned long long)) != hipSuccess) return nullptr;
         bases.push_back(b); base_dev.push_back(dev);
     }
     int slot = -1, used = 0;
@@ -443,7 +472,7 @@ static unsigned long long* l1_word_for(hipStream_t stream)
         owners.push_back(stream); owner_dev.push_back(dev);
         slot = used;
     }
-    return b + slot;
+    return b + slot * kL1Group;
 }
 
 static int l1_forward_impl(int64_t n, const float* a, const float* b, float scale, float* sum, float* partial, float* d_a, bool grad, void* stream_)
