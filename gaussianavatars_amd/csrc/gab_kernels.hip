@@ -17,6 +17,7 @@
 #include "launch_prof.h"
 #include "lib_common.h"
 #include "bind_math.h"
+#include "wave_reduce.h"
 
 namespace gab {
 
@@ -40,22 +41,8 @@ constexpr int WS_DT = 320;   // 3
 constexpr int WS_DPF = 324;  // 36
 constexpr int WS_DJ = 384;   // 15
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_f(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
-}
-// 64-lane sum; the result is valid in lanes 48..63
-__device__ __forceinline__ float wave_sum_hi(float v)
-{
-    v += dpp_f<0xB1, 0xf>(v);
-    v += dpp_f<0x4E, 0xf>(v);
-    v += dpp_f<0x141, 0xf>(v);
-    v += dpp_f<0x140, 0xf>(v);
-    v += dpp_f<0x142, 0xa>(v);
-    v += dpp_f<0x143, 0xc>(v);
-    return v;
-}
+using wave_reduce::dpp_f;
+using wave_reduce::wave_sum_hi;   // 64-lane sum; the result is valid in lanes 48..63
 
 __device__ __forceinline__ float beta_at(const float* shape, const float* expr, int n_shape, int l)
 {

@@ -1,12 +1,12 @@
 // gev_kernels.hip -- evaluation and export (include/gev.h): the statistics of an image pair that training_report (train.py:256-309) and
 // metrics.py take with 30 - 40 composed torch launches, in two; and the bytes render.py:41 writes, in one.
 //
-// k_pair_stats has the structure of gls::k_l1_ssim_fwd (gls_kernels.hip): per 32x16 output tile the 42x26 halo of both images goes to LDS
-// once (zero padding as F.conv2d(padding=5)), the five windowed moments are formed separably (11 horizontal taps into LDS, 11 vertical taps
-// in registers, every output adding its taps in the order k = 0 .. 10), and the tile's sums go out as one fixed-order partial.  What differs:
-// the halo load reads either layout of include/gev.h and applies the load transform ONCE per pixel, there are no derivative planes, and the
-// tile also sums (a-b)^2 -- in fp64, because PSNR is new here and has no tolerance to inherit.  k_reduce_accumulate adds the tiles of every
-// plane in fp64 and, as its last act, forms the image's figures and adds them to the device-resident running sums.
+// k_pair_stats forms the five windowed moments of a tile with the window of ssim_window.h, the one gls::k_l1_ssim_fwd (gls_kernels.hip) is
+// built from, and the tile's sums go out as one fixed-order partial.  Its own: the halo load reads either layout of include/gev.h and applies
+// the load transform ONCE per pixel, there are no derivative planes, the SSIM map is A * Bv * (1 / (Cv * D)) (gls forms a product of two
+// quotients: DESIGN.md section 17), and the tile also sums (a-b)^2 -- in fp64, because PSNR is new here and has no tolerance to inherit.
+// k_reduce_accumulate adds the tiles of every plane in fp64 and, as its last act, forms the image's figures and adds them to the
+// device-resident running sums.
 // Built with -ffp-contract=off: to_byte's multiply and add must round separately (the bytes are torch's bytes).
 #include <hip/hip_runtime.h>
 
@@ -16,55 +16,20 @@
 #include "../../include/gev.h"
 #include "launch_prof.h"
 #include "lib_common.h"
+#include "ssim_window.h"
+#include "wave_reduce.h"
 
 namespace gev {
 
-constexpr int WIN = GEV_SSIM_WINDOW, RAD = WIN / 2;
-constexpr int TX = 32, TY = 16, HX = TX + 2 * RAD, HY = TY + 2 * RAD, HXS = HX + 2;   // (row stride 44: 16-byte rows)
-constexpr float SSIM_C1 = 0.01f * 0.01f, SSIM_C2 = 0.03f * 0.03f;
+using namespace ssim_window;
+using wave_reduce::wave_sum_hi;   // sum over the 64 lanes, valid in lane 63 (float and double)
+static_assert(WIN == GEV_SSIM_WINDOW, "include/gev.h publishes the window ssim_window.h applies");
 
-struct Window {
-    float w[WIN];
-};
 // one tile's sums: |a-b| and the SSIM map in fp32 (the arithmetic of gls_l1_ssim_forward), (a-b)^2 in fp64
 struct TileSums {
     float l1, ss;
     double sq;
 };
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_f(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_d(double v)   // (the two halves move separately; a lane outside the row mask reads +0.0, as in dpp_f)
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-// sum over the 64 lanes, valid in lane 63
-__device__ __forceinline__ float wave_sum_hi(float v)
-{
-    v += dpp_f<0xB1, 0xf>(v);
-    v += dpp_f<0x4E, 0xf>(v);
-    v += dpp_f<0x141, 0xf>(v);
-    v += dpp_f<0x140, 0xf>(v);
-    v += dpp_f<0x142, 0xa>(v);
-    v += dpp_f<0x143, 0xc>(v);
-    return v;
-}
-__device__ __forceinline__ double wave_sum_hi(double v)
-{
-    v += dpp_d<0xB1, 0xf>(v);
-    v += dpp_d<0x4E, 0xf>(v);
-    v += dpp_d<0x141, 0xf>(v);
-    v += dpp_d<0x140, 0xf>(v);
-    v += dpp_d<0x142, 0xa>(v);
-    v += dpp_d<0x143, 0xc>(v);
-    return v;
-}
 
 // render.py:41 for one value: mul(255), add_(0.5), clamp_(0, 255), to(uint8).  Four roundings, none fused (-ffp-contract=off).  fmaxf sends a
 // NaN to 0 and the clamp leaves nothing outside [0, 255] for the conversion, so no input faults or is undefined here.
@@ -83,23 +48,17 @@ __device__ __forceinline__ float transformed(float x, int transform)
     return x;
 }
 
-// loads the (HY x HX) halo of one plane into LDS, transformed, zero outside the image
+// the halo of one plane of either layout, transformed ONCE per pixel
 __device__ __forceinline__ void load_halo(float (*dst)[HXS], const void* __restrict__ img, int layout, int transform, int C, int H, int W, int plane,
                                           int x0, int y0, int tid)
 {
     const int b = plane / C, c = plane - b * C;
     const float* __restrict__ fplane = (const float*)img + (size_t)plane * H * W;
     const unsigned char* __restrict__ bimg = (const unsigned char*)img + (size_t)b * H * W * C + c;
-    for (int i = tid; i < HY * HX; i += 256) {
-        const int r = i / HX, col = i - r * HX;
-        const int gy = y0 + r - RAD, gx = x0 + col - RAD;
-        float v = 0.f;
-        if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-            const size_t px = (size_t)gy * W + gx;
-            v = layout == GEV_U8_INTERLEAVED ? (float)bimg[px * C] / 255.f : transformed(fplane[px], transform);
-        }
-        dst[r][col] = v;
-    }
+    ssim_window::load_halo(dst, H, W, x0, y0, tid, [=](int gy, int gx) {
+        const size_t px = (size_t)gy * W + gx;
+        return layout == GEV_U8_INTERLEAVED ? (float)bimg[px * C] / 255.f : transformed(fplane[px], transform);
+    });
 }
 
 __global__ __launch_bounds__(256) void k_pair_stats(int C, int H, int W, const void* __restrict__ img1, int layout1, const void* __restrict__ img2,
@@ -114,50 +73,18 @@ __global__ __launch_bounds__(256) void k_pair_stats(int C, int H, int W, const v
     load_halo(sx, img1, layout1, transform, C, H, W, plane, x0, y0, tid);
     load_halo(sy, img2, layout2, transform, C, H, W, plane, x0, y0, tid);
     __syncthreads();
-    if (tid < HY * (TX / 4)) {   // horizontal taps: row r, columns c0 .. c0 + 3
-        const int r = tid >> 3, c0 = (tid & 7) * 4;
-        float xs[WIN + 3], ys[WIN + 3];
-#pragma unroll
-        for (int k = 0; k < WIN + 3; ++k) { xs[k] = sx[r][c0 + k]; ys[k] = sy[r][c0 + k]; }
-        float o[5][4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float a = 0.f, b = 0.f, aa = 0.f, bb = 0.f, ab = 0.f;
-#pragma unroll
-            for (int k = 0; k < WIN; ++k) {
-                const float x = xs[j + k], y = ys[j + k], w = win.w[k];
-                a += w * x;
-                b += w * y;
-                aa += w * (x * x);
-                bb += w * (y * y);
-                ab += w * (x * y);
-            }
-            o[0][j] = a; o[1][j] = b; o[2][j] = aa; o[3][j] = bb; o[4][j] = ab;
-        }
-#pragma unroll
-        for (int m = 0; m < 5; ++m) *reinterpret_cast<float4*>(&hq[m][r][c0]) = make_float4(o[m][0], o[m][1], o[m][2], o[m][3]);
-    }
+    horizontal_pair(sx, sy, hq, win, tid);
     __syncthreads();
     const int tx = tid & 31, ty0 = (tid >> 5) * 2;   // vertical taps: column tx, rows ty0 and ty0 + 1
     float col[5][WIN + 1];
-#pragma unroll
-    for (int m = 0; m < 5; ++m)
-#pragma unroll
-        for (int k = 0; k < WIN + 1; ++k) col[m][k] = hq[m][ty0 + k][tx];
+    load_columns(hq, tx, ty0, col);
     float l1 = 0.f, ss = 0.f;
     double sq = 0.0;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        float mu1 = 0.f, mu2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-        for (int k = 0; k < WIN; ++k) {
-            const float w = win.w[k];
-            mu1 += w * col[0][j + k];
-            mu2 += w * col[1][j + k];
-            e11 += w * col[2][j + k];
-            e22 += w * col[3][j + k];
-            e12 += w * col[4][j + k];
-        }
+        float e[5];   // E[x], E[y], E[x^2], E[y^2], E[xy]
+        window_sums(col, win, j, e);
+        const float mu1 = e[0], mu2 = e[1], e11 = e[2], e22 = e[3], e12 = e[4];
         const int ty = ty0 + j, px = x0 + tx, py = y0 + ty;
         if (px < W && py < H) {
             const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
@@ -174,14 +101,16 @@ __global__ __launch_bounds__(256) void k_pair_stats(int C, int H, int W, const v
     l1 = wave_sum_hi(l1);
     ss = wave_sum_hi(ss);
     sq = wave_sum_hi(sq);
-    if ((tid & 63) == 63) { red[0][tid >> 6] = l1; red[1][tid >> 6] = ss; redd[tid >> 6] = sq; }
+    block_sum_post(red[0], l1, tid);
+    block_sum_post(red[1], ss, tid);
+    block_sum_post(redd, sq, tid);
     __syncthreads();
     if (tid == 0) {
         const size_t blk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
         TileSums t;
-        t.l1 = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        t.ss = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-        t.sq = (redd[0] + redd[1]) + (redd[2] + redd[3]);
+        t.l1 = block_sum(red[0]);
+        t.ss = block_sum(red[1]);
+        t.sq = block_sum(redd);
         partial[blk] = t;
     }
 }
@@ -282,23 +211,8 @@ __global__ __launch_bounds__(256) void k_to_u8_any(long long pixels, int C, int 
 }  // namespace gev
 
 // ---------------------------------------------------------------------------------------------------------------
-static gev::Window make_window()
-{
-    // utils/loss_utils.py:23-25: exp(-(x - 5)^2 / (2 * 1.5^2)) held in fp32, divided by its fp32 sum
-    gev::Window w;
-    float sum = 0.f;
-    for (int x = 0; x < gev::WIN; ++x) {
-        w.w[x] = (float)std::exp(-(double)((x - gev::RAD) * (x - gev::RAD)) / (2.0 * 1.5 * 1.5));
-        sum += w.w[x];
-    }
-    for (int x = 0; x < gev::WIN; ++x) w.w[x] /= sum;
-    return w;
-}
-
-static bool image_args_ok(int32_t B, int32_t C, int32_t H, int32_t W)
-{
-    return B > 0 && C > 0 && H > 0 && W > 0 && (int64_t)B * C <= 65535 && (H + gev::TY - 1) / gev::TY <= 65535;
-}
+using ssim_window::image_args_ok;
+using ssim_window::make_window;
 static bool layout_ok(int32_t l) { return l == GEV_F32_PLANAR || l == GEV_U8_INTERLEAVED; }
 
 static int stats_impl(int32_t B, int32_t C, int32_t H, int32_t W, const void* a, int32_t a_layout, const void* b, int32_t b_layout, int32_t transform,
@@ -314,7 +228,7 @@ static int stats_impl(int32_t B, int32_t C, int32_t H, int32_t W, const void* a,
     if ((a_layout == GEV_F32_PLANAR && ((uintptr_t)a & 3)) || (b_layout == GEV_F32_PLANAR && ((uintptr_t)b & 3)) || ((uintptr_t)per_view & 3))
         return fail(GEV_E_ARG, "float buffers must be 4-byte aligned");
     hipStream_t stream = (hipStream_t)stream_;
-    const dim3 grid((W + gev::TX - 1) / gev::TX, (H + gev::TY - 1) / gev::TY, B * C);
+    const dim3 grid = ssim_window::tile_grid(B, C, H, W);
     PROF_LAUNCH(gev::k_pair_stats, grid, dim3(256), 0, stream, C, H, W, a, a_layout, b, b_layout, transform, make_window(), (gev::TileSums*)partial);
     LAUNCH_CHECK(GEV_E_HIP, "k_pair_stats");
     PROF_LAUNCH(gev::k_reduce_accumulate, dim3(1), dim3(256), 0, stream, (const gev::TileSums*)partial, B, C, (int)(grid.x * grid.y),
@@ -331,8 +245,7 @@ const char* gev_last_error(void) { return g_err; }
 int64_t gev_partial_floats(int32_t B, int32_t C, int32_t H, int32_t W)
 {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
-    const int64_t tiles = (int64_t)((W + gev::TX - 1) / gev::TX) * ((H + gev::TY - 1) / gev::TY) * B * C;
-    return tiles * (int64_t)(sizeof(gev::TileSums) / sizeof(float));
+    return ssim_window::tile_count(B, C, H, W) * (int64_t)(sizeof(gev::TileSums) / sizeof(float));
 }
 
 int gev_pair_stats(int32_t B, int32_t C, int32_t H, int32_t W, const void* a, int32_t a_layout, const void* b, int32_t b_layout, int32_t transform,

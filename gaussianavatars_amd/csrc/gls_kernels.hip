@@ -1,12 +1,11 @@
 // gls_kernels.hip -- fused L1 + SSIM image loss (forward / backward) and the densification statistics
 // update: the training-step neighbours of the render path (include/gls.h).
 //
-// SSIM forward, per 16x16 output tile: the 26x26 halo of both images goes to LDS once (zero padding as
-// F.conv2d(padding=5)), the five windowed moments E[x], E[y], E[x^2], E[y^2], E[xy] are formed separably
-// (11 horizontal taps into LDS, 11 vertical taps in registers), the SSIM map and |x-y| are reduced per
-// workgroup into fixed-order partials, and the three partial derivatives the backward needs are written
-// as planes.  Backward: the same separable window over those three planes, combined with x and y.
-// All of it is HBM-trivial (5 MB images); the point is ~4 launches instead of ~60.
+// SSIM forward, per output tile: the five windowed moments E[x], E[y], E[x^2], E[y^2], E[xy] are formed by the
+// separable window of ssim_window.h (halo to LDS, horizontal taps into LDS, vertical taps in registers), the
+// SSIM map and |x-y| are reduced per workgroup into fixed-order partials, and the three partial derivatives
+// the backward needs are written as planes.  Backward: the same window over those three planes, combined
+// with x and y.  All of it is HBM-trivial (5 MB images); the point is ~4 launches instead of ~60.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -15,49 +14,20 @@
 #include "../../include/gls.h"
 #include "launch_prof.h"
 #include "lib_common.h"
+#include "ssim_window.h"
+#include "wave_reduce.h"
 
 namespace gls {
 
-constexpr int WIN = GLS_SSIM_WINDOW, RAD = WIN / 2;
-// Round 4: 32 x 16 output tiles (a 42 x 26 halo: 2.1 x the pixels instead of 2.6 x at 16 x 16) and REGISTER-BLOCKED taps -- a thread of the
-// horizontal pass owns four neighbouring columns of a row and reads their 14 inputs once (28 LDS reads for four outputs where one output at a
-// time took 22 each), a thread of the vertical pass owns two neighbouring rows of a column (12 reads per moment for two outputs instead of
-// 22).  Every output still adds its eleven taps in the order k = 0 .. 10, so the values are the bits of the round-1 kernel.
-// Measured (rocprofv3, train workload): k_l1_ssim_fwd 24.4 -> 24.2 us, k_l1_ssim_bwd 25.4 -> 22.6 us -- the LDS reads were not what bounds the pair: the
-// forward writes 15.9 MB of derivative planes and the backward reads them back with their halos (~38 MB each way per kernel at ~3 TB/s).
-constexpr int TX = 32, TY = 16, HX = TX + 2 * RAD, HY = TY + 2 * RAD, HXS = HX + 2;   // (row stride 44: 16-byte rows)
-constexpr float SSIM_C1 = 0.01f * 0.01f, SSIM_C2 = 0.03f * 0.03f;
+// the tile scheme of the SSIM kernels (32 x 16 tiles, the halo, the register-blocked taps and what was measured) is ssim_window.h's
+using namespace ssim_window;
+using wave_reduce::wave_sum_hi;   // sum over the 64 lanes, valid in lane 63
+static_assert(WIN == GLS_SSIM_WINDOW, "include/gls.h publishes the window ssim_window.h applies");
 
-struct Window {
-    float w[WIN];
-};
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_f(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
-}
-// sum over the 64 lanes, valid in lane 63
-__device__ __forceinline__ float wave_sum_hi(float v)
-{
-    v += dpp_f<0xB1, 0xf>(v);
-    v += dpp_f<0x4E, 0xf>(v);
-    v += dpp_f<0x141, 0xf>(v);
-    v += dpp_f<0x140, 0xf>(v);
-    v += dpp_f<0x142, 0xa>(v);
-    v += dpp_f<0x143, 0xc>(v);
-    return v;
-}
-
-// loads the (HY x HX) halo of one plane into LDS, zero outside the image
+// the halo of one fp32 plane
 __device__ __forceinline__ void load_halo(float (*dst)[HXS], const float* __restrict__ plane, int H, int W, int x0, int y0, int tid)
 {
-    for (int i = tid; i < HY * HX; i += 256) {
-        const int r = i / HX, c = i - r * HX;
-        const int gy = y0 + r - RAD, gx = x0 + c - RAD;
-        const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-        dst[r][c] = in ? plane[(size_t)gy * W + gx] : 0.f;
-    }
+    ssim_window::load_halo(dst, H, W, x0, y0, tid, [=](int gy, int gx) { return plane[(size_t)gy * W + gx]; });
 }
 
 __global__ __launch_bounds__(256, 6) void k_l1_ssim_fwd(int H, int W, const float* __restrict__ img1, const float* __restrict__ img2,
@@ -73,49 +43,17 @@ __global__ __launch_bounds__(256, 6) void k_l1_ssim_fwd(int H, int W, const floa
     load_halo(sx, img1 + poff, H, W, x0, y0, tid);
     load_halo(sy, img2 + poff, H, W, x0, y0, tid);
     __syncthreads();
-    if (tid < HY * (TX / 4)) {   // horizontal taps: row r, columns c0 .. c0 + 3
-        const int r = tid >> 3, c0 = (tid & 7) * 4;
-        float xs[WIN + 3], ys[WIN + 3];
-#pragma unroll
-        for (int k = 0; k < WIN + 3; ++k) { xs[k] = sx[r][c0 + k]; ys[k] = sy[r][c0 + k]; }
-        float o[5][4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float a = 0.f, b = 0.f, aa = 0.f, bb = 0.f, ab = 0.f;
-#pragma unroll
-            for (int k = 0; k < WIN; ++k) {
-                const float x = xs[j + k], y = ys[j + k], w = win.w[k];
-                a += w * x;
-                b += w * y;
-                aa += w * (x * x);
-                bb += w * (y * y);
-                ab += w * (x * y);
-            }
-            o[0][j] = a; o[1][j] = b; o[2][j] = aa; o[3][j] = bb; o[4][j] = ab;
-        }
-#pragma unroll
-        for (int m = 0; m < 5; ++m) *reinterpret_cast<float4*>(&hq[m][r][c0]) = make_float4(o[m][0], o[m][1], o[m][2], o[m][3]);
-    }
+    horizontal_pair(sx, sy, hq, win, tid);
     __syncthreads();
     const int tx = tid & 31, ty0 = (tid >> 5) * 2;   // vertical taps: column tx, rows ty0 and ty0 + 1
     float col[5][WIN + 1];
-#pragma unroll
-    for (int m = 0; m < 5; ++m)
-#pragma unroll
-        for (int k = 0; k < WIN + 1; ++k) col[m][k] = hq[m][ty0 + k][tx];
+    load_columns(hq, tx, ty0, col);
     float l1 = 0.f, ss = 0.f;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        float mu1 = 0.f, mu2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-        for (int k = 0; k < WIN; ++k) {
-            const float w = win.w[k];
-            mu1 += w * col[0][j + k];
-            mu2 += w * col[1][j + k];
-            e11 += w * col[2][j + k];
-            e22 += w * col[3][j + k];
-            e12 += w * col[4][j + k];
-        }
+        float e[5];   // E[x], E[y], E[x^2], E[y^2], E[xy]
+        window_sums(col, win, j, e);
+        const float mu1 = e[0], mu2 = e[1], e11 = e[2], e22 = e[3], e12 = e[4];
         const int ty = ty0 + j, px = x0 + tx, py = y0 + ty;
         if (px < W && py < H) {
             // (no contraction from here on, and the map as the product of two quotients: for an identical pair A == C and B == D bit for
@@ -140,11 +78,12 @@ __global__ __launch_bounds__(256, 6) void k_l1_ssim_fwd(int H, int W, const floa
     }
     l1 = wave_sum_hi(l1);
     ss = wave_sum_hi(ss);
-    if ((tid & 63) == 63) { red[0][tid >> 6] = l1; red[1][tid >> 6] = ss; }
+    block_sum_post(red[0], l1, tid);
+    block_sum_post(red[1], ss, tid);
     __syncthreads();
     if (tid == 0) {
         const size_t blk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        partial[blk] = make_float2((red[0][0] + red[0][1]) + (red[0][2] + red[0][3]), (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]));
+        partial[blk] = make_float2(block_sum(red[0]), block_sum(red[1]));
     }
 }
 
@@ -162,11 +101,10 @@ __global__ __launch_bounds__(256) void k_reduce_partials(const float2* __restric
     }
     a = wave_sum_hi(a);
     b = wave_sum_hi(b);
-    if ((tid & 63) == 63) { red[0][tid >> 6] = a; red[1][tid >> 6] = b; }
+    block_sum_post(red[0], a, tid);
+    block_sum_post(red[1], b, tid);
     __syncthreads();
-    if (tid == 0)
-        sums[blockIdx.x] = make_float2(scale * ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])),
-                                       scale * ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])));
+    if (tid == 0) sums[blockIdx.x] = make_float2(scale * block_sum(red[0]), scale * block_sum(red[1]));
 }
 
 __global__ __launch_bounds__(256) void k_l1_ssim_bwd(int C, int H, int W, const float* __restrict__ img1, const float* __restrict__ img2,
@@ -182,45 +120,20 @@ __global__ __launch_bounds__(256) void k_l1_ssim_bwd(int C, int H, int W, const 
 #pragma unroll
     for (int q = 0; q < 3; ++q) load_halo(sm[q], maps + q * map_stride + poff, H, W, x0, y0, tid);
     __syncthreads();
-    if (tid < HY * (TX / 4)) {   // horizontal taps of the three derivative planes: row r, columns c0 .. c0 + 3
-        const int r = tid >> 3, c0 = (tid & 7) * 4;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            float v[WIN + 3];
-#pragma unroll
-            for (int k = 0; k < WIN + 3; ++k) v[k] = sm[q][r][c0 + k];
-            float o[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float a = 0.f;
-#pragma unroll
-                for (int k = 0; k < WIN; ++k) a += win.w[k] * v[j + k];
-                o[j] = a;
-            }
-            *reinterpret_cast<float4*>(&hq[q][r][c0]) = make_float4(o[0], o[1], o[2], o[3]);
-        }
-    }
+    horizontal_planes<3>(sm, hq, win, tid);   // the three derivative planes
     __syncthreads();
     const int tx = tid & 31, ty0 = (tid >> 5) * 2;
     float col[3][WIN + 1];
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-        for (int k = 0; k < WIN + 1; ++k) col[q][k] = hq[q][ty0 + k][tx];
+    load_columns(hq, tx, ty0, col);
     const int img = plane / C;   // dL/d(mean |x - y|) and dL/d(mean ssim) of this image; a missing one is zero
     float2 gi = make_float2(g_l1 ? g_l1[(size_t)img * g_stride] : 0.f, g_ssim ? g_ssim[(size_t)img * g_stride] : 0.f);
     gi.x *= scale;
     gi.y *= scale;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        float ca = 0.f, cb = 0.f, cc = 0.f;
-#pragma unroll
-        for (int k = 0; k < WIN; ++k) {
-            const float w = win.w[k];
-            ca += w * col[0][j + k];
-            cb += w * col[1][j + k];
-            cc += w * col[2][j + k];
-        }
+        float cw[3];
+        window_sums(col, win, j, cw);
+        const float ca = cw[0], cb = cw[1], cc = cw[2];
         const int px = x0 + tx, py = y0 + ty0 + j;
         if (px < W && py < H) {
 #pragma clang fp contract(off)   // (2 x cb and y cc rounded alike: they cancel exactly where cc == -2 cb, see k_l1_ssim_fwd)
@@ -317,9 +230,9 @@ __global__ __launch_bounds__(256) void k_l1_reduce(const float2* __restrict__ pa
     float s = 0.f;
     for (int i = tid; i < count; i += 256) s += partial[i].x;
     s = wave_sum_hi(s);
-    if ((tid & 63) == 63) red[tid >> 6] = s;
+    block_sum_post(red, s, tid);
     __syncthreads();
-    if (tid == 0) *sum = scale * ((red[0] + red[1]) + (red[2] + red[3]));
+    if (tid == 0) *sum = scale * block_sum(red);
 }
 __global__ __launch_bounds__(256) void k_l1_bwd(long long n, const float* __restrict__ a, const float* __restrict__ b,
                                                  const float* __restrict__ g, float scale, float* __restrict__ d_a)
@@ -366,18 +279,9 @@ __global__ __launch_bounds__(256) void k_add_densify_stats(int P, const unsigned
 }  // namespace gls
 
 // ---------------------------------------------------------------------------------------------------------------
-static gls::Window make_window()
-{
-    // utils/loss_utils.py:23-25: exp(-(x - 5)^2 / (2 * 1.5^2)) held in fp32, divided by its fp32 sum
-    gls::Window w;
-    float sum = 0.f;
-    for (int x = 0; x < gls::WIN; ++x) {
-        w.w[x] = (float)std::exp(-(double)((x - gls::RAD) * (x - gls::RAD)) / (2.0 * 1.5 * 1.5));
-        sum += w.w[x];
-    }
-    for (int x = 0; x < gls::WIN; ++x) w.w[x] /= sum;
-    return w;
-}
+using ssim_window::image_args_ok;
+using ssim_window::make_window;
+using ssim_window::tile_grid;
 static const int kL1Blocks = 1024;
 
 extern "C" {
@@ -385,15 +289,10 @@ extern "C" {
 int gls_abi_version(void) { return GLS_ABI_VERSION; }
 const char* gls_last_error(void) { return g_err; }
 
-static bool image_args_ok(int32_t B, int32_t C, int32_t H, int32_t W)
-{
-    return B > 0 && C > 0 && H > 0 && W > 0 && (int64_t)B * C <= 65535 && (H + gls::TY - 1) / gls::TY <= 65535;
-}
-
 int64_t gls_partial_floats(int32_t B, int32_t C, int32_t H, int32_t W)
 {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return 2 * kL1Blocks;
-    const int64_t tiles = (int64_t)((W + gls::TX - 1) / gls::TX) * ((H + gls::TY - 1) / gls::TY) * B * C;
+    const int64_t tiles = ssim_window::tile_count(B, C, H, W);
     return 2 * (tiles > kL1Blocks ? tiles : kL1Blocks);
 }
 
@@ -403,7 +302,7 @@ int gls_l1_ssim_forward(int32_t B, int32_t C, int32_t H, int32_t W, const float*
     if (!image_args_ok(B, C, H, W)) return fail(GLS_E_ARG, "bad image shape (%d,%d,%d,%d)", B, C, H, W);
     if (!img1 || !img2 || !sums || !partial) return fail(GLS_E_ARG, "null pointer");
     hipStream_t stream = (hipStream_t)stream_;
-    const dim3 grid((W + gls::TX - 1) / gls::TX, (H + gls::TY - 1) / gls::TY, B * C);
+    const dim3 grid = tile_grid(B, C, H, W);
     const size_t stride = (size_t)B * C * H * W;
     PROF_LAUNCH(gls::k_l1_ssim_fwd, grid, dim3(256), 0, stream, H, W, img1, img2, make_window(), maps, stride, (float2*)partial);
     LAUNCH_CHECK(GLS_E_HIP, "k_l1_ssim_fwd");
@@ -418,7 +317,7 @@ static int l1_ssim_backward_impl(int32_t B, int32_t C, int32_t H, int32_t W, con
     if (!image_args_ok(B, C, H, W)) return fail(GLS_E_ARG, "bad image shape (%d,%d,%d,%d)", B, C, H, W);
     if (!img1 || !img2 || !maps || !d_img1 || g_stride < 0) return fail(GLS_E_ARG, "null pointer");
     hipStream_t stream = (hipStream_t)stream_;
-    const dim3 grid((W + gls::TX - 1) / gls::TX, (H + gls::TY - 1) / gls::TY, B * C);
+    const dim3 grid = tile_grid(B, C, H, W);
     const size_t stride = (size_t)B * C * H * W;
     PROF_LAUNCH(gls::k_l1_ssim_bwd, grid, dim3(256), 0, stream, C, H, W, img1, img2, maps, stride, make_window(), g_l1, g_ssim, g_stride, scale, d_img1);
     LAUNCH_CHECK(GLS_E_HIP, "k_l1_ssim_bwd");

@@ -40,6 +40,7 @@
 #define GSR_RANK_BIN_THREADS 1024 // threads per workgroup of k_rcount / k_rdscatter / k_rscatter (<= GSR_BIN_BLOCKS workgroups: 16 waves each keep the SIMDs busy)
 
 #include "bind_math.h"
+#include "wave_reduce.h"
 
 namespace gsr {
 
@@ -140,52 +141,11 @@ __device__ __forceinline__ float ndc2pix(float v, int S)
 
 __device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
-// ---- wave64 reductions on the DPP network -------------------------------------------------
-// xor-butterfly inside each 16-lane row (quad_perm, row_half_mirror, row_mirror), then
-// row_bcast:15 into rows 1,3 and row_bcast:31 into rows 2,3: lanes 48..63 end up holding the
-// full 64-lane sum.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_f(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
-}
-__device__ __forceinline__ float wave_sum_hi(float v)
-{
-    v += dpp_f<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
-    v += dpp_f<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
-    v += dpp_f<0x141, 0xf>(v);  // row_half_mirror
-    v += dpp_f<0x140, 0xf>(v);  // row_mirror
-    v += dpp_f<0x142, 0xa>(v);  // row_bcast:15 -> rows 1,3
-    v += dpp_f<0x143, 0xc>(v);  // row_bcast:31 -> rows 2,3
-    return v;                   // valid in lanes 48..63
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
-{
-    // ds_swizzle-free max: butterfly through readlane-able DPP moves
-    auto mx = [](uint32_t a, uint32_t b) { return a > b ? a : b; };
-    v = mx(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false));
-    v = mx(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, false));
-    v = mx(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, false));
-    v = mx(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xf, 0xf, false));
-    uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)v, 0);
-    uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)v, 16);
-    uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)v, 32);
-    uint32_t d = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
-    return mx(mx(a, b), mx(c, d));
-}
-
-// inclusive prefix sum across the 64 lanes in six DPP adds (row_shr inside the rows of 16, then the row totals broadcast to the
-// rows above): no LDS crossbar round trips (ds_bpermute), which is what __shfl_up costs per step
-__device__ __forceinline__ uint32_t wave_scan_incl_u32(uint32_t v)
-{
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);   // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);   // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);   // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);   // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1, 3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2, 3
-    return v;
-}
+// the wave64 reductions on the DPP network (wave_reduce.h), under the names the rasterizer's kernels have always called them by
+using wave_reduce::dpp_f;
+using wave_reduce::wave_max_u32;
+using wave_reduce::wave_scan_incl_u32;
+using wave_reduce::wave_sum_hi;
 
 // ---- tile-rect expansion shared by the counting and the scatter pass ------------------------
 // Calls f(tile_id, k) for every tile of the rect.  Splats touching <= SMALL tiles are expanded by

@@ -1,4 +1,4 @@
-// lib_common.h -- the host-side error plumbing every single-file library (gab, gls, gmr, gop, grl) has behind its C ABI: the text
+// lib_common.h -- the host-side error plumbing every single-file library (gab, gls, gmr, gop, grl, gdc, gev, gfs) has behind its C ABI: the text
 // <lib>_last_error() returns, fail() that writes it, and the check that follows a launch.  Each library is its own shared object and
 // includes this once, so the `static` buffer below is that library's own (and each calling thread's own).  libgsr keeps its own in
 // gsr_api.hip.
