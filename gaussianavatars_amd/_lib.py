@@ -65,8 +65,8 @@ LIBS = {}
 
 
 def _lib_path(tag, env=None):
-    """The in-tree build of a library, or the file the environment variable `env` names (kernel experiments build variants side by side:
-    tools/exp_build.sh).  An override that does not exist is an error, never a fallback."""
+    """The in-tree build of a library, or the file the environment variable `env` names (a variant built side by side, such as
+    `make timeline`'s libgsr_timeline.so).  An override that does not exist is an error, never a fallback."""
     return (env and os.environ.get(env)) or os.path.join(_HERE, f"lib{tag}_hip.so")
 
 

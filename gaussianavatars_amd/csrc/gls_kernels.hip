@@ -385,8 +385,7 @@ static int l1_forward_impl(int64_t n, const float* a, const float* b, float scal
     static const bool fused_on = [] { const char* e = getenv("GLS_L1_FUSED"); return !(e && e[0] == '0'); }();
     unsigned long long* word = (fused_on && n < (1ll << 26)) ? l1_word_for(stream) : nullptr;
     if (word) {
-        static const int fmax = [] { const char* e = getenv("GLS_L1_BLOCKS"); const int v = e ? atoi(e) : 0; return v > 0 && v <= 255 ? v : 255; }();   // (A/B runs)
-        static const int fthreads = [] { const char* e = getenv("GLS_L1_THREADS"); const int v = e ? atoi(e) : 0; return v == 256 || v == 512 || v == 1024 ? v : 1024; }();
+        constexpr int fmax = 255, fthreads = 1024;   // workgroups (at most) and threads of each
         const int wide = (int)(((n >> 2) + fthreads - 1) / fthreads);
         const int fb = wide < 1 ? 1 : (wide > fmax ? fmax : wide);
         if (grad) PROF_LAUNCH(gls::k_l1_fwd_1g, dim3(fb), dim3(fthreads), 0, stream, (long long)n, a, b, (float2*)partial, scale, d_a, word, sum);

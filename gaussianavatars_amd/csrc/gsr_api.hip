@@ -50,7 +50,7 @@ int fail(int code, const char* fmt, ...)
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // ---- host mailbox: a small ring of 8-byte slots in mapped pinned memory -----------------------
-// k_tile_scan posts (seq << 40 | I) with one system-scope store; gsr_forward spins on the slot.
+// The binning's scan (k_rdscatter's last workgroup / k_qscan_glob) posts (seq << 40 | I) with one system-scope store; gsr_forward spins on the slot.
 struct Mailbox {
     static constexpr int kSlots = 256;        // ring of the waiting forwards
     static constexpr int kPersistent = 2 * GSR_COUNT_SLOTS;   // after the ring: the count slots of the deferred forwards (GsrSettings.deferred_count),
@@ -131,6 +131,15 @@ gsr::Settings to_dev_settings(const GsrSettings* s)
     return d;
 }
 
+// GsrSettings.tile_culling: 0..4 and 6 (include/gsr.h).  5 selected the per-tile bitonic sort, which is gone: an error, not a fallback to the
+// rank path (an old A/B script would then compare the rank path with itself)
+int check_tile_culling(int32_t tile_culling)
+{
+    if (tile_culling == 5) return fail(GSR_E_ARG, "tile_culling 5: the per-tile sort was removed (binning modes are 0..4 and 6)");
+    if (tile_culling < 0 || tile_culling > 6) return fail(GSR_E_ARG, "tile_culling %d: binning modes are 0..4 and 6", (int)tile_culling);
+    return 0;
+}
+
 int check_settings(const GsrSettings* s)
 {
     if (!s) return fail(GSR_E_ARG, "settings is NULL");
@@ -139,13 +148,13 @@ int check_settings(const GsrSettings* s)
     if (!s->bg || !s->viewmatrix || !s->projmatrix || !s->campos) return fail(GSR_E_ARG, "bg/viewmatrix/projmatrix/campos must be device pointers");
     if (s->sh_degree < 0 || s->sh_degree > 3) return fail(GSR_E_ARG, "sh_degree must be in 0..3");
     if (s->deferred_count < 0 || s->deferred_count > GSR_COUNT_SLOTS) return fail(GSR_E_ARG, "deferred_count must be 0 or a slot in 1..%d", GSR_COUNT_SLOTS);
+    if (int rc = check_tile_culling(s->tile_culling)) return rc;
     return 0;
 }
 
 // GsrSettings.fast_blend as it applies to a frame: the exact kernels serve the deterministic mode (whose fixed-point scales are
-// derived for the exact partial sums) and the per-tile sort path (whose binning kernels read the conic from the per-splat record,
-// where the fast mode keeps it pre-scaled).  The forward and the backward of a frame evaluate this on the same inputs.
-bool fast_effective(const GsrSettings* s, const GsrBinningLayout& bl) { return s->fast_blend != 0 && s->deterministic == 0 && bl.path != 2; }
+// derived for the exact partial sums).  The forward and the backward of a frame evaluate this on the same inputs.
+bool fast_effective(const GsrSettings* s) { return s->fast_blend != 0 && s->deterministic == 0; }
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, size class): the attribute sticks, and the call is not
 // something to repeat per frame (nor inside a stream capture)
@@ -301,15 +310,12 @@ static bool production_params(int32_t P, size_t tiles, int32_t tile_culling, siz
     *chunks = c; *nb = b;
     return true;
 }
-// Binning path of a frame: 1 production (depth-ordered scatter, gsr_binning.hip), 2 round 1's per-tile bitonic sort (tile_culling 5:
-// kept for A/B runs), 0 the rank path (gsr_rank.hip: splats ranked by depth once, tiles ordered through an LDS bitmap).
+// Binning path of a frame: 1 production (depth-ordered scatter, gsr_binning.hip), 0 the rank path (gsr_rank.hip: splats ranked by depth
+// once, tiles ordered through an LDS bitmap).
 static int binning_path(int32_t P, size_t tiles, int32_t tile_culling, size_t* chunks, size_t* nb)
 {
     if (production_params(P, tiles, tile_culling, chunks, nb)) return 1;
-    if (tile_culling == 5) return 2;
-    // about 256 splats per depth bucket (GSR_RANK_BUCKET_SPLATS: experiment knob, a power of two up to 1024 -- a bucket is sorted in the registers
-    // of 256 threads up to 2048 keys)
-    static const size_t per = [] { const char* e = getenv("GSR_RANK_BUCKET_SPLATS"); const long v = e ? atol(e) : 0; return (size_t)(v >= 64 && v <= 1024 ? v : 256); }();
+    const size_t per = 256;   // splats per depth bucket, about (a bucket is sorted in the registers of 256 threads up to 2048 keys)
     size_t b = 16;
     while (b < (size_t)GSR_RANK_MAX_BUCKETS && b * per < (size_t)P) b <<= 1;
     *nb = b;
@@ -319,20 +325,20 @@ static int binning_path(int32_t P, size_t tiles, int32_t tile_culling, size_t* c
 int gsr_binning_layout(int64_t capacity, int32_t width, int32_t height, int32_t P, int32_t tile_culling, GsrBinningLayout* o)
 {
     if (!o || capacity < 0 || width <= 0 || height <= 0 || P < 0) return fail(GSR_E_ARG, "gsr_binning_layout: bad arguments");
+    if (int rc = check_tile_culling(tile_culling)) return rc;
     const size_t tiles = (size_t)((width + GSR_BLOCK_X - 1) / GSR_BLOCK_X) * (size_t)((height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y);
     const size_t cap = (size_t)capacity, A = 256, n = (size_t)P;
     size_t chunks, nb;
     const int path = binning_path(P, tiles, tile_culling, &chunks, &nb);
-    const bool prod = path == 1, rankp = path == 0, old = path == 2;
+    const bool prod = path == 1, rankp = path == 0;
     const bool lists = tile_culling == 0 || tile_culling == 2;     // the reference-format key / point lists are materialised
-    const bool dsort = prod || rankp;                              // the splats are depth-sorted
     const size_t Q = 4 * tiles, qw = (Q + 3) / 4;
     const int lgx = (width + GSR_BLOCK_X - 1) / GSR_BLOCK_X;
-    const bool no_hist = rankp ? gsr::rank_direct(lgx, (int)tiles) : tiles > (size_t)GSR_LDS_HIST_TILES;   // no per-workgroup histograms: L2 atomics
+    const bool no_hist = rankp && gsr::rank_direct(lgx, (int)tiles);   // no per-workgroup tile histograms: L2 atomics
     size_t off = align_up(sizeof(gsr::BinHeader), A);  // header + statistics slots (gsr_device.h: BinHeader)
-    o->keys = off;        off = align_up(off + (old || (rankp && lists) ? cap * 8 : 0), A);
-    o->point_list = off;  off = align_up(off + (old || rankp ? cap * 4 : 0), A);
-    o->qlist = off;       off = align_up(off + (!prod && lists ? cap * 4 * 4 : 0), A);
+    o->keys = off;        off = align_up(off + (rankp && lists ? cap * 8 : 0), A);
+    o->point_list = off;  off = align_up(off + (rankp ? cap * 4 : 0), A);
+    o->qlist = off;       off = align_up(off + (rankp && lists ? cap * 4 * 4 : 0), A);
     o->qpos = off;        off = align_up(off + (prod ? cap * 4 : cap * 4 * 4), A);
     o->qcount = off;      off = align_up(off + tiles * 16, A);
     o->qstart = off;      off = align_up(off + tiles * 16, A);
@@ -343,14 +349,14 @@ int gsr_binning_layout(int64_t capacity, int32_t width, int32_t height, int32_t 
     o->tile_order = off;  off = align_up(off + tiles * 4, A);
     const size_t blocks = rankp ? (size_t)GSR_RANK_BLOCKS : (size_t)GSR_BIN_BLOCKS;
     o->block_hist = off;  off = align_up(off + (prod || no_hist ? 0 : blocks * tiles * 4), A);
-    o->dkeys = off;       off = align_up(off + (dsort ? n * 8 : 0), A);
-    o->dtmp = off;        off = align_up(off + (dsort ? n * 8 : 0), A);
+    o->dkeys = off;       off = align_up(off + n * 8, A);
+    o->dtmp = off;        off = align_up(off + n * 8, A);
     o->order = off;       off = align_up(off + (prod ? n * 4 : 0), A);
-    o->bcount = off;      off = align_up(off + (dsort ? nb * 4 : 0), A);
-    o->bstart = off;      off = align_up(off + (dsort ? nb * 4 : 0), A);
-    o->bcursor = off;     off = align_up(off + (dsort ? nb * 4 : 0), A);
+    o->bcount = off;      off = align_up(off + nb * 4, A);
+    o->bstart = off;      off = align_up(off + nb * 4, A);
+    o->bcursor = off;     off = align_up(off + nb * 4, A);
     o->border = off;      off = align_up(off + (prod ? nb * 4 : 0), A);
-    o->bhist = off;       off = align_up(off + (dsort ? blocks * nb * 4 : 0), A);
+    o->bhist = off;       off = align_up(off + blocks * nb * 4, A);
     o->qhist = off;       off = align_up(off + (prod ? chunks * qw * 4 : 0), A);
     o->qprefix = off;     off = align_up(off + (prod ? chunks * Q * 4 : 0), A);
     o->qmask = off;       off = align_up(off + (prod ? n * GSR_WALK_MASKS * 8 : 0), A);
@@ -435,7 +441,7 @@ static int forward_impl(const GsrSettings* settings, int32_t P, int32_t M, const
     if (P > 0 && (!means3D || !opacities || !radii || !geom)) return fail(GSR_E_ARG, "NULL splat buffer");
     if (!binning || !img) return fail(GSR_E_ARG, "NULL state buffer");
     if (binning_capacity < 0 || binning_capacity >= (1ll << 32)) return fail(GSR_E_ARG, "binning_capacity out of range");
-    {   // the rank and per-tile sort paths address the four quadrant streams of a tile as 32-bit ELEMENT offsets 4 * start + q * n into qpos
+    {   // the rank path addresses the four quadrant streams of a tile as 32-bit ELEMENT offsets 4 * start + q * n into qpos
         GsrBinningLayout probe;
         gsr_binning_layout(0, settings->image_width, settings->image_height, P, settings->tile_culling, &probe);
         if (probe.path != 1 && binning_capacity > (1ll << 30))
@@ -464,7 +470,7 @@ static int forward_impl(const GsrSettings* settings, int32_t P, int32_t M, const
     const bool prod = bl.path == 1;                   // depth-ordered scatter into the quadrant streams (gsr_binning.hip)
 
     gsr::Settings ds = to_dev_settings(settings);
-    ds.fast_blend = fast_effective(settings, bl) ? 1 : 0;
+    ds.fast_blend = fast_effective(settings) ? 1 : 0;
     if (prod) {
         HIP_TRY(hipMemsetAsync(hdr, 0, sizeof(gsr::BinHeader), stream));   // k_preprocess accumulates the frame statistics into it
     } else if (P == 0) {   // otherwise k_preprocess zeroes both
@@ -540,6 +546,9 @@ static int forward_impl(const GsrSettings* settings, int32_t P, int32_t M, const
         if (can && ((balanced == 1 && ilv > 0) || balanced == 2)) rank_ilv = -2;
     }
     slot_holds_frame(deferred ? settings->deferred_count - 1 : GSR_COUNT_SLOTS, dev_id, rankp ? settings->image_width : 0, settings->image_height);
+    // Optimistic launch: the rest of the frame is enqueued against the caller's capacity before the
+    // host knows I; every kernel re-checks *total_dev <= capacity on the device and does nothing
+    // otherwise.  The host then waits only for the scan (early in the frame), not for the frame.
     const unsigned long long cap = (unsigned long long)binning_capacity;
     uint32_t* tile_order = (uint32_t*)(b + bl.tile_order);
     uint32_t* qpos = (uint32_t*)(b + bl.qpos);
@@ -604,7 +613,7 @@ static int forward_impl(const GsrSettings* settings, int32_t P, int32_t M, const
             hipLaunchKernelGGL(gsr::k_qscatter, dim3(walk_blocks), dim3(64), walk_lds, stream, qa);
             KERNEL_CHECK("k_qscatter", stream, dbg);
         }
-    } else if (rankp) {
+    } else {
         // ---- rank path: depth-rank the splats once, order every tile's instances through an LDS bitmap (gsr_rank.hip) ----
         const uint32_t nb = (uint32_t)bl.nb;
         const int bin_blocks = pblocks < GSR_RANK_BLOCKS ? pblocks : GSR_RANK_BLOCKS;
@@ -616,11 +625,10 @@ static int forward_impl(const GsrSettings* settings, int32_t P, int32_t M, const
             if (int rc = ensure_dynamic_lds((const void*)gsr::k_rcount, (size_t)count_lds)) return rc;
         }
         // the scatter's dynamic LDS: the tile histogram, then (when they fit the 160 KB beside it and the sort's 16 KB of keys) the staging
-        // rows of the balanced expansion -- GSR_RSCATTER_BALANCED=0 keeps the lockstep form (A/B runs)
+        // rows of the balanced expansion (else: the lockstep form)
         const bool one_band_lds = (int)bl.nbands <= 1;
         const size_t stage_bytes = GSR_RSCATTER_STAGE_BYTES(one_band_lds), hist_al = (hist_bytes + 15) & ~(size_t)15;
-        static const bool balanced_on = [] { const char* e = getenv("GSR_RSCATTER_BALANCED"); return !(e && e[0] == '0'); }();
-        const bool balanced = balanced_on && hist_al + stage_bytes + 20 * 1024 <= 160 * 1024;
+        const bool balanced = hist_al + stage_bytes + 20 * 1024 <= 160 * 1024;
         const int stage_off = balanced ? (int)hist_al : -1;
         const size_t scatter_lds = balanced ? hist_al + stage_bytes : hist_bytes;
         if (scatter_lds > 48 * 1024)
@@ -711,64 +719,7 @@ static int forward_impl(const GsrSettings* settings, int32_t P, int32_t M, const
                                cap, (const unsigned long long*)total_dev);
             KERNEL_CHECK("k_tile_rank", stream, dbg);
         }
-    } else {
-    // round 1's per-tile bitonic sort (tile_culling 5).  Binning workgroups: each owns a contiguous chunk of splats and an LDS histogram over the tiles
-    const int bin_blocks = pblocks < GSR_BIN_BLOCKS ? pblocks : GSR_BIN_BLOCKS;
-    uint32_t* block_hist = (uint32_t*)(b + bl.block_hist);
-    // (grids beyond GSR_LDS_HIST_TILES tiles -- past ~3200x3200 px -- fall back to per-instance L2 atomics)
-    const size_t hist_bytes = tiles > GSR_LDS_HIST_TILES ? 0 : (size_t)tiles * sizeof(uint32_t);
-    if (hist_bytes > 48 * 1024) {
-        if (int rc = ensure_dynamic_lds((const void*)gsr::k_count<false>, (size_t)hist_bytes)) return rc;
-        if (int rc = ensure_dynamic_lds((const void*)gsr::k_count<true>, (size_t)hist_bytes)) return rc;
-        if (int rc = ensure_dynamic_lds((const void*)gsr::k_scatter<false>, (size_t)hist_bytes)) return rc;
-        if (int rc = ensure_dynamic_lds((const void*)gsr::k_scatter<true>, (size_t)hist_bytes)) return rc;
     }
-    const bool cull = settings->tile_culling != 0;
-    if (pblocks > 0) {
-        TIMED(GSR_K_COUNT, stream);
-        hipLaunchKernelGGL(cull ? gsr::k_count<true> : gsr::k_count<false>, dim3(bin_blocks), dim3(256), hist_bytes, stream, P, gx, tiles,
-                           (const ushort4*)pa.rect, (const uint32_t*)pa.tiles_touched, (const float4*)pa.grec, tile_count, rect_total, block_hist);
-        KERNEL_CHECK("k_count", stream, dbg);
-    }
-    uint32_t* tile_start = (uint32_t*)(b + bl.tile_start);
-    uint32_t* tile_cursor = (uint32_t*)(b + bl.tile_cursor);
-    uint2* ranges = (uint2*)(b + bl.ranges);
-    {
-        TIMED(GSR_K_TILE_SCAN, stream);
-        hipLaunchKernelGGL(gsr::k_tile_scan, dim3(1), dim3(1024), 0, stream, tiles, (const uint32_t*)tile_count, tile_start, tile_cursor,
-                           ranges, tile_order, total_dev, slot_dev, seq, post_cap);
-        KERNEL_CHECK("k_tile_scan", stream, dbg);
-    }
-
-    // Optimistic launch: the rest of the frame is enqueued against the caller's capacity before the
-    // host knows I; every kernel re-checks *total_dev <= capacity on the device and does nothing
-    // otherwise.  The host then waits only for the scan (early in the frame), not for the frame.
-    unsigned long long* keys = (unsigned long long*)(b + bl.keys);
-    uint32_t* point_list = (uint32_t*)(b + bl.point_list);
-    if (pblocks > 0) {
-        TIMED(GSR_K_SCATTER, stream);
-        hipLaunchKernelGGL(cull ? gsr::k_scatter<true> : gsr::k_scatter<false>, dim3(bin_blocks), dim3(256), hist_bytes, stream, P, gx, tiles,
-                           (const float*)pa.depths, (const ushort4*)pa.rect, (const uint32_t*)pa.tiles_touched, (const float4*)pa.grec,
-                           (const uint32_t*)tile_start, tile_cursor, keys, cap, (const unsigned long long*)total_dev,
-                           (const uint32_t*)block_hist);
-        KERNEL_CHECK("k_scatter", stream, dbg);
-    }
-    {
-        // per-tile sort + quadrant streams: three size classes, the long (few) ones first.  Launched even when
-        // P == 0 so that every tile's quadrant counters are written.
-        TIMED(GSR_K_TILE_SORT, stream);
-        auto sort_class = [&](auto kernel, int threads, uint32_t n_lo, uint32_t n_hi) {
-            hipLaunchKernelGGL(kernel, dim3(tiles), dim3(threads), 0, stream, n_lo, n_hi, gx, (const uint32_t*)tile_order,
-                               (const uint32_t*)tile_count, (const uint32_t*)tile_start, keys, write_lists ? point_list : nullptr, write_lists ? qlist : nullptr, qpos, qcount, qstart,
-                               (const float4*)pa.grec, cap,
-                               (const unsigned long long*)total_dev);
-        };
-        sort_class(gsr::k_tile_sort<GSR_SORT_XL_KEYS, 1024>, 1024, (uint32_t)GSR_SORT_LDS_KEYS, 0xFFFFFFFFu);
-        sort_class(gsr::k_tile_sort<GSR_SORT_LDS_KEYS, 1024>, 1024, (uint32_t)GSR_SORT_SMALL_KEYS, (uint32_t)GSR_SORT_LDS_KEYS);
-        sort_class(gsr::k_tile_sort<GSR_SORT_SMALL_KEYS, 256>, 256, 0u, (uint32_t)GSR_SORT_SMALL_KEYS);
-        KERNEL_CHECK("k_tile_sort", stream, dbg);
-    }
-    }   // per-tile sort path
     {
         TIMED(GSR_K_RENDER, stream);
         const bool infer = ds.forward_only;   // (torch.no_grad() / fps benchmarks: the instances without the backward's bookkeeping)
@@ -880,7 +831,7 @@ static int backward_impl(const GsrSettings* settings, int32_t P, int32_t M, cons
     const char* b = (const char*)binning;
     const char* im = (const char*)img;
     gsr::Settings ds = to_dev_settings(settings);
-    ds.fast_blend = fast_effective(settings, bl) ? 1 : 0;
+    ds.fast_blend = fast_effective(settings) ? 1 : 0;
     float* grad_scratch = (float*)(g + gl.acc);   // zeroed by the forward (and by the previous backward)
     long long* acc64 = (long long*)(g + gl.acc64);
     uint32_t* gmax = (uint32_t*)(const_cast<char*>(im) + il.gmax);   // scratch word of the image state
@@ -892,33 +843,25 @@ static int backward_impl(const GsrSettings* settings, int32_t P, int32_t M, cons
     }
     if (num_rendered > 0) {
         TIMED(GSR_K_RENDER_BWD, stream);
-        if (ds.fast_blend && settings->fast_blend != 2) {   // fast blend: the record-parallel kernel (fast_blend == 2 keeps the pixel-parallel walk: A/B runs)
-            // a fixed grid: every wave takes the units of its list in turn (gsr.h: GsrImageLayout.units), so the size only sets how many
-            // share the work -- about one unit per wave at 100 k splats and 802 x 550, never more workgroups than the old one per (tile, segment)
-#ifndef GSR_EXP_RP_GRID
-#define GSR_EXP_RP_GRID 3072
-#endif
-#ifndef GSR_RP_WAVES_PER_WG_DEFAULT
-#define GSR_RP_WAVES_PER_WG_DEFAULT 1
-#endif
+        if (ds.fast_blend) {   // fast blend: the record-parallel kernel
+            // a fixed number of waves: every wave takes the units of its list in turn (gsr.h: GsrImageLayout.units), so the size only sets how many
+            // share the work -- about one unit per wave at 100 k splats and 802 x 550, never more waves than four per (tile, segment)
             int rp_grid = gx * gy * GSR_BWD_SEGMENTS;
-            rp_grid = rp_grid < GSR_EXP_RP_GRID ? (rp_grid + 15) / 16 * 16 : GSR_EXP_RP_GRID;   // a multiple of GSR_UNIT_LISTS / 4 workgroups: every list sees the same stride
+            rp_grid = rp_grid < 3072 ? (rp_grid + 15) / 16 * 16 : 3072;   // a multiple of GSR_UNIT_LISTS / 4: every list sees the same stride
             // ONE wave per workgroup (round 6): a wave gets about one unit and units differ in cost by the half-rows that reach them (1 .. 16); in a
             // workgroup of four the slot of a finished wave stays taken until the slowest of the four is done
-            static const int rp_waves = [] { const char* e = getenv("GSR_RP_WAVES_PER_WG"); const int v = e ? atoi(e) : 0; return v == 1 || v == 2 || v == 4 ? v : GSR_RP_WAVES_PER_WG_DEFAULT; }();
-            auto* const rp_k = rp_waves == 1 ? &gsr::k_render_bwd_rp<1> : (rp_waves == 2 ? &gsr::k_render_bwd_rp<2> : &gsr::k_render_bwd_rp<4>);
-            hipLaunchKernelGGL(rp_k, dim3(rp_grid * (4 / rp_waves)), dim3(64 * rp_waves), 0, stream, ds,
+            hipLaunchKernelGGL(gsr::k_render_bwd_rp, dim3(rp_grid * 4), dim3(64), 0, stream, ds,
                                (const uint32_t*)(b + bl.qstart), (const uint32_t*)(b + bl.qcount), (const float4*)(g + gl.grec), (const uint32_t*)(b + bl.qpos),
                                (const float*)(im + il.final_T), (const uint32_t*)(im + il.n_contrib_q), dL_dpix, grad_scratch,
                                (const float*)(im + il.c_final), (const float4*)(im + il.ck), gx * gy,
                                (unsigned long long)binning_capacity, (const unsigned long long*)b, (const uint32_t*)(im + il.units));
-        } else {
-        auto* const render_bwd = det ? &gsr::k_render_bwd<true, false> : (ds.fast_blend ? &gsr::k_render_bwd<false, true> : &gsr::k_render_bwd<false, false>);
-        hipLaunchKernelGGL(render_bwd, dim3(gx * gy * GSR_BWD_SEGMENTS), dim3(256), 0, stream, ds, (const uint32_t*)(b + bl.tile_order),
-                           (const uint32_t*)(b + bl.qstart), (const uint32_t*)(b + bl.qcount), (const float4*)(g + gl.grec), (const uint32_t*)(b + bl.qpos),
-                           (const float*)(im + il.final_T), (const uint32_t*)(im + il.n_contrib_q), dL_dpix, grad_scratch,
-                           (const float*)(im + il.c_final), (const float4*)(im + il.ck), gx * gy, acc64, (const uint32_t*)gmax,
-                           (unsigned long long)binning_capacity, (const unsigned long long*)b);
+        } else {   // exact blend: the pixel-parallel walk, with fixed-point sums in the deterministic mode
+            auto* const render_bwd = det ? &gsr::k_render_bwd<true> : &gsr::k_render_bwd<false>;
+            hipLaunchKernelGGL(render_bwd, dim3(gx * gy * GSR_BWD_SEGMENTS), dim3(256), 0, stream, ds, (const uint32_t*)(b + bl.tile_order),
+                               (const uint32_t*)(b + bl.qstart), (const uint32_t*)(b + bl.qcount), (const float4*)(g + gl.grec), (const uint32_t*)(b + bl.qpos),
+                               (const float*)(im + il.final_T), (const uint32_t*)(im + il.n_contrib_q), dL_dpix, grad_scratch,
+                               (const float*)(im + il.c_final), (const float4*)(im + il.ck), gx * gy, acc64, (const uint32_t*)gmax,
+                               (unsigned long long)binning_capacity, (const unsigned long long*)b);
         }
         KERNEL_CHECK("k_render_bwd", stream, dbg);
     }

@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void k_gmax(size_t n, const float* __restrict_
     if ((threadIdx.x & 63) == 0 && m) atomicMax(gmax, m);
 }
 
-template <bool DET, bool FAST>
+template <bool DET>
 __global__ __launch_bounds__(256) void k_render_bwd(Settings s, const uint32_t* __restrict__ tile_order, const uint32_t* __restrict__ qstart,
                                                      const uint32_t* __restrict__ qcount,
                                                      const float4* __restrict__ grec, const uint32_t* __restrict__ qpos,
@@ -180,7 +180,6 @@ __global__ __launch_bounds__(256) void k_render_bwd(Settings s, const uint32_t* 
                 R.ex[u] = 0;
             }
             R.op[u] = R.a[u][5];
-            if (FAST) R.op[u] = *(const __attribute__((address_space(4))) float*)(recb + off + 40);   // fast-blend record: slot 5 holds log2(opacity), slot 10 the opacity
             R.id[u] = P.p[u];   // the stream entry IS the splat index
         }
     };
@@ -201,14 +200,8 @@ __global__ __launch_bounds__(256) void k_render_bwd(Settings s, const uint32_t* 
             dys[u] = R.a[u][1] - pixy;
             // hardware 2^x (v_exp_f32, ~1 ulp) instead of the forward's 13-instruction bit-reproducible polynomial: the backward
             // is compared with a tolerance, and a record whose alpha sits within an ulp of 1/255 flipping in or out is noise
-            float power;
-            if constexpr (FAST) {   // fast blend: the record's conic is pre-scaled by -log2(e)/2 (exactly the forward's expression)
-                power = __builtin_fmaf(__builtin_fmaf(R.a[u][3], dys[u], R.a[u][2] * dxs[u]), dxs[u], (R.a[u][4] * dys[u]) * dys[u]);
-                G[u] = __builtin_amdgcn_exp2f(power);
-            } else {
-                power = -0.5f * (R.a[u][2] * dxs[u] * dxs[u] + R.a[u][4] * dys[u] * dys[u]) - R.a[u][3] * dxs[u] * dys[u];
-                G[u] = __builtin_amdgcn_exp2f(power * 1.4426950408889634f);
-            }
+            const float power = -0.5f * (R.a[u][2] * dxs[u] * dxs[u] + R.a[u][4] * dys[u] * dys[u]) - R.a[u][3] * dxs[u] * dys[u];
+            G[u] = __builtin_amdgcn_exp2f(power * 1.4426950408889634f);
             alpha[u] = sel_min(0.99f, R.op[u] * G[u]);
             hit[u] = (jp + u) < last && power <= 0.0f && alpha[u] >= 1.0f / 255.0f;
             id[uo + u] = R.id[u];
@@ -244,17 +237,12 @@ __global__ __launch_bounds__(256) void k_render_bwd(Settings s, const uint32_t* 
             vv[0] = w * g0;
             vv[1] = w * g1;
             vv[2] = w * g2;
-            if constexpr (FAST) {   // the two position sums leave without the conic: k_preprocess_bwd, which has it, forms A sx + B sy, C sy + B sx per splat
-                vv[3] = ax;
-                vv[4] = ay;
-            } else {
-                vv[3] = ax * R.a[u][2] + ay * R.a[u][3];          // x (-W/2) = dL/dmean2D.x
-                vv[4] = ay * R.a[u][4] + ax * R.a[u][3];          // x (-H/2) = dL/dmean2D.y
-            }
+            vv[3] = ax * R.a[u][2] + ay * R.a[u][3];          // x (-W/2) = dL/dmean2D.x
+            vv[4] = ay * R.a[u][4] + ax * R.a[u][3];          // x (-H/2) = dL/dmean2D.y
             vv[5] = ax * dxs[u];                              // x (-1/2) = dL/dconic (a, b, c)
             vv[6] = ax * dys[u];
             vv[7] = ay * dys[u];
-            vv[8] = FAST ? q : Gh * dL_dalpha;                // fast blend: times the opacity (k_preprocess_bwd divides once per splat)
+            vv[8] = Gh * dL_dalpha;
             T = Tn;
             last_alpha = al;
             last_one_m = one_m;
@@ -333,13 +321,10 @@ __global__ __launch_bounds__(256) void k_render_bwd(Settings s, const uint32_t* 
 #endif
 }
 
-template __global__ void k_render_bwd<false, true>(Settings, const uint32_t*, const uint32_t*, const uint32_t*, const float4*, const uint32_t*, const float*,
-                                                   const uint32_t*, const float*, float*, const float*, const float4*, int, long long*, const uint32_t*,
-                                                   unsigned long long, const unsigned long long*);
-template __global__ void k_render_bwd<false, false>(Settings, const uint32_t*, const uint32_t*, const uint32_t*, const float4*, const uint32_t*, const float*,
+template __global__ void k_render_bwd<false>(Settings, const uint32_t*, const uint32_t*, const uint32_t*, const float4*, const uint32_t*, const float*,
                                              const uint32_t*, const float*, float*, const float*, const float4*, int, long long*, const uint32_t*,
                                              unsigned long long, const unsigned long long*);
-template __global__ void k_render_bwd<true, false>(Settings, const uint32_t*, const uint32_t*, const uint32_t*, const float4*, const uint32_t*, const float*,
+template __global__ void k_render_bwd<true>(Settings, const uint32_t*, const uint32_t*, const uint32_t*, const float4*, const uint32_t*, const float*,
                                             const uint32_t*, const float*, float*, const float*, const float4*, int, long long*, const uint32_t*,
                                             unsigned long long, const unsigned long long*);
 
@@ -358,7 +343,7 @@ template __global__ void k_render_bwd<true, false>(Settings, const uint32_t*, co
 // accumulator once per segment.  Per-pixel operands are wave-uniform (one LDS table per wave, broadcast reads); two pixels share every
 // arithmetic instruction through packed fp32 (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32), the scans of four pixels are issued
 // interleaved so that the DPP read-after-write distance is covered by useful instructions.
-// Same results as the pixel-parallel fast kernel up to summation order (tests/test_fast_blend_gpu.py holds both to the oracle).
+// tests/test_fast_blend_gpu.py holds it to the oracle; it is the fast blend's only backward.
 // ------------------------------------------------------------------------------------------
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef float f4 __attribute__((ext_vector_type(4)));
@@ -378,11 +363,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
                  GSR_SCAN4_STEP(OP, "row_bcast:31 row_mask:0xc bank_mask:0xf")                         \
                  : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
 
-#ifdef GSR_EXP_RP_WAVES
-__attribute__((amdgpu_waves_per_eu(GSR_EXP_RP_WAVES, GSR_EXP_RP_WAVES)))
-#endif
-template <int WPB>
-__global__ __launch_bounds__(64 * WPB) void k_render_bwd_rp(Settings s, const uint32_t* __restrict__ qstart,
+__global__ __launch_bounds__(64) void k_render_bwd_rp(Settings s, const uint32_t* __restrict__ qstart,
                                                         const uint32_t* __restrict__ qcount, const float4* __restrict__ grec,
                                                         const uint32_t* __restrict__ qpos, const float* __restrict__ final_T,
                                                         const uint32_t* __restrict__ n_contrib_q, const float* __restrict__ dL_dpix,
@@ -391,8 +372,11 @@ __global__ __launch_bounds__(64 * WPB) void k_render_bwd_rp(Settings s, const ui
                                                         const unsigned long long* __restrict__ total_dev, const uint32_t* __restrict__ units)
 {
     if (*total_dev > capacity) return;
-    __shared__ __attribute__((aligned(16))) float tab_all[WPB][32 * 12];   // per wave: the pixel table (below)
-    __shared__ float xpose_all[WPB][64 * 9];                                // per wave: the nine sums of every lane on their way out
+    // ONE wave per workgroup (waves share nothing).  The wave's index is still read from threadIdx: written with the constant
+    // folded, the compiler schedules the prologue differently, and this kernel's instruction stream is kept as it was measured.
+    constexpr int WPB = 1;
+    __shared__ __attribute__((aligned(16))) float tab_all[WPB][32 * 12];   // the wave's pixel table (below)
+    __shared__ float xpose_all[WPB][64 * 9];                                // the nine sums of every lane on their way out
     constexpr int CH = GSR_BWD_SEGMENT;          // records per chunk = lanes in use (60 of 64)
     static_assert(CH <= 64 && CH > 32, "a chunk of the stream has to fit the wave");
     const int W = s.W, H = s.H;
@@ -402,7 +386,6 @@ __global__ __launch_bounds__(64 * WPB) void k_render_bwd_rp(Settings s, const ui
     // ---- the wave's UNITS (gsr.h: GsrImageLayout.units): entries p, p + stride, ... of list (wave id mod GSR_UNIT_LISTS); every unit is a
     // (tile, quadrant, segment) the forward found a contributor in, so a wave that gets one has work (round 3 launched a workgroup per (tile,
     // segment): four of five found nothing, and the waves of the others were tied to the four quadrants whether those reached the segment or not)
-    // (the waves of a workgroup share nothing: the launch decides how many there are -- gsr_api.hip)
     constexpr uint32_t wpb = (uint32_t)WPB;
     const uint32_t wid = (uint32_t)blockIdx.x * wpb + (uint32_t)wave_in_wg, list = wid % (uint32_t)GSR_UNIT_LISTS;
     const uint32_t ustride = (uint32_t)gridDim.x * wpb / (uint32_t)GSR_UNIT_LISTS;
@@ -414,11 +397,7 @@ __global__ __launch_bounds__(64 * WPB) void k_render_bwd_rp(Settings s, const ui
     for (uint32_t up = wid / (uint32_t)GSR_UNIT_LISTS; up < ucount; up += ustride) {
     // (from the END of the list: the forward appends a quadrant's units when its walk is over, so the deep quadrants -- whose open-ended last segment
     //  is many chunks for one wave -- come last in the list; taken first they are not the kernel's tail: template-like frame 109.8 -> see DESIGN.md 7.6)
-#ifndef GSR_EXP_RP_FORWARD_ORDER
     const uint32_t unit = (uint32_t)__builtin_amdgcn_readfirstlane((int)ulist[ucount - 1u - up]);
-#else
-    const uint32_t unit = (uint32_t)__builtin_amdgcn_readfirstlane((int)ulist[up]);
-#endif
     const int seg = (int)(unit & 15u), wave = (int)((unit >> 4) & 3u), tile = (int)(unit >> 6);   // `wave`: the quadrant
     const int tile_x = tile % gx, tile_y = tile / gx;
     const int nq = (int)qcount[4 * tile + wave];
@@ -481,11 +460,9 @@ __global__ __launch_bounds__(64 * WPB) void k_render_bwd_rp(Settings s, const ui
             if (!rm) continue;
             const float dy = yq - (float)r;
             const float Bdy = cB * dy, Cdy2 = (cC * dy) * dy;
-#ifndef GSR_EXP_NO_ROW_SUMS
             // the six position moments of tq = G dL/dG: dy is the same for the row's eight pixels, so the row adds up (sum tq, sum tq dx, sum tq dx^2)
             // and the three dy-weighted sums are formed once per row (4 packed operations per pixel pair instead of 8)
             f2 rs0 = {0.f, 0.f}, rs1 = rs0, rs2 = rs0;
-#endif
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 if (!((rm >> (4 * h)) & 0xFu)) continue;
@@ -504,21 +481,14 @@ __global__ __launch_bounds__(64 * WPB) void k_render_bwd_rp(Settings s, const ui
                     const f2 G = {__builtin_amdgcn_exp2f(pw.x), __builtin_amdgcn_exp2f(pw.y)};
                     const f2 araw = op * G;
                     const int l0 = __float_as_int(t[e][2].z), l1 = __float_as_int(t[e][2].w);
-#ifdef GSR_EXP_HI_TEST
-                    a0m[e].x = (l0 > jrec && pw.x <= 0.0f && araw.x >= 1.0f / 255.0f) ? araw.x : 0.0f;
-                    a0m[e].y = (l1 > jrec && pw.y <= 0.0f && araw.y >= 1.0f / 255.0f) ? araw.y : 0.0f;
-#else
                     a0m[e].x = (l0 > jrec && araw.x >= 1.0f / 255.0f) ? araw.x : 0.0f;
                     a0m[e].y = (l1 > jrec && araw.y >= 1.0f / 255.0f) ? araw.y : 0.0f;
-#endif
                     al[e] = f2{__builtin_fminf(0.99f, a0m[e].x), __builtin_fminf(0.99f, a0m[e].y)};
                     const f2 om = 1.0f - al[e];
                     rv[e] = f2{__builtin_amdgcn_rcpf(om.x), __builtin_amdgcn_rcpf(om.y)};
                     R[e] = rv[e];
                 }
-#ifndef GSR_EXP_RP_NOSCAN
                 GSR_SCAN4("v_mul_f32_dpp", R[0].x, R[0].y, R[1].x, R[1].y);
-#endif
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
                     const f2 Te = {t[e][0].x, t[e][0].y};
@@ -528,9 +498,7 @@ __global__ __launch_bounds__(64 * WPB) void k_render_bwd_rp(Settings s, const ui
                     aT[e] = al[e] * Tj[e];
                     Pw[e] = aT[e] * cg[e];      // w = alpha T (c . dL/dC); scanned in place
                 }
-#ifndef GSR_EXP_RP_NOSCAN
                 GSR_SCAN4("v_add_f32_dpp", Pw[0].x, Pw[0].y, Pw[1].x, Pw[1].y);
-#endif
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
                     const f2 Sx = {t[e][0].z, t[e][0].w};
@@ -542,20 +510,10 @@ __global__ __launch_bounds__(64 * WPB) void k_render_bwd_rp(Settings s, const ui
                     a0 += aT[e] * g0;
                     a1 += aT[e] * g1;
                     a2 += aT[e] * g2;
-#ifndef GSR_EXP_NO_ROW_SUMS
                     const f2 ax = tq * dx[e];
                     rs0 += tq;
                     rs1 += ax;
                     rs2 += ax * dx[e];
-#else
-                    const f2 ax = tq * dx[e], ay = tq * dy;
-                    a3 += ax;                                           // k_preprocess_bwd forms A sx + B sy, C sy + B sx and the constant factors
-                    a4 += ay;
-                    a5 += ax * dx[e];
-                    a6 += ax * dy;
-                    a7 += ay * dy;
-                    a8 += tq;                                           // / opacity, once per splat
-#endif
                     if (more) {
                         // state at the chunk's lower end for the chunk below: lane CH-1 holds the lowest entry -- the transmittance in front of it
                         // and, inclusive of it, the sum behind
@@ -570,20 +528,17 @@ __global__ __launch_bounds__(64 * WPB) void k_render_bwd_rp(Settings s, const ui
                     }
                 }
             }
-#ifndef GSR_EXP_NO_ROW_SUMS
             a3 += rs1;                                                  // k_preprocess_bwd forms A sx + B sy, C sy + B sx and the constant factors
             a4 += rs0 * dy;
             a5 += rs2;
             a6 += rs1 * dy;
             a7 += rs0 * (dy * dy);
             a8 += rs0;                                                  // / opacity, once per splat
-#endif
         }
         // ---- nine sums per record.  A lane adding its own nine would send 60 different cache lines per instruction through the L2 atomic
         // units (measured: the kernel three times slower than the walk it replaces); instead the sums cross the wave through LDS and leave
         // record-major -- lane e of pass i carries element 64 i + e of the (record, component) matrix, so each record's nine floats are
         // consecutive lanes of one instruction and reach its 48-byte accumulator as one burst.
-#ifndef GSR_EXP_RP_NOATOMIC
         {
             const float v[9] = {a0.x + a0.y, a1.x + a1.y, a2.x + a2.y, a3.x + a3.y, a4.x + a4.y, a5.x + a5.y, a6.x + a6.y, a7.x + a7.y, a8.x + a8.y};
 #pragma unroll
@@ -597,26 +552,14 @@ __global__ __launch_bounds__(64 * WPB) void k_render_bwd_rp(Settings s, const ui
                 const float val = xs[63 * i + lane];
                 const uint32_t rid = (uint32_t)__builtin_amdgcn_ds_bpermute(rl << 2, (int)idx);   // its splat
                 const bool live = lane < 63 && rl < CH && (hi - 1 - rl) < nq;
-#ifdef GSR_EXP_RP_PLAINSTORE    // timing experiment: the sums stay live, nothing is added (a store no value ever triggers)
-                if (live && val == 12345.678f) acc[(size_t)GSR_ACC_STRIDE * rid + c] = val;
-#else
                 if (live && val != 0.f) unsafeAtomicAdd(acc + (size_t)GSR_ACC_STRIDE * rid + c, val);
-#endif
             }
         }
-#endif
         if (!more) break;
         hi = lo;
     }
     }   // units
 }
-
-template __global__ void k_render_bwd_rp<1>(Settings, const uint32_t*, const uint32_t*, const float4*, const uint32_t*, const float*, const uint32_t*, const float*, float*, const float*,
-                                             const float4*, int, unsigned long long, const unsigned long long*, const uint32_t*);
-template __global__ void k_render_bwd_rp<2>(Settings, const uint32_t*, const uint32_t*, const float4*, const uint32_t*, const float*, const uint32_t*, const float*, float*, const float*,
-                                             const float4*, int, unsigned long long, const unsigned long long*, const uint32_t*);
-template __global__ void k_render_bwd_rp<4>(Settings, const uint32_t*, const uint32_t*, const float4*, const uint32_t*, const float*, const uint32_t*, const float*, float*, const float*,
-                                             const float4*, int, unsigned long long, const unsigned long long*, const uint32_t*);
 
 // ------------------------------------------------------------------------------------------
 

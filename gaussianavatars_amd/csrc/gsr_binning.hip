@@ -18,7 +18,7 @@
 //   k_qscatter   per chunk : same walk; slot = qstart[q] + qprefix[chunk][q] + (LDS cursor++): a stable append, no atomics
 //                            between waves, no sort, no per-instance record gather
 //
-// Streams come out exactly as the parity path's (k_tile_sort epilogue): the entries of quadrant q are the splats whose tile-level
+// Streams come out exactly as the parity path's (gsr_rank.hip: k_tile_rank): the entries of quadrant q are the splats whose tile-level
 // snug rect holds q's tile and whose ellipse reaches q, in (depth, index) order -- tests compare them entry for entry.
 #include "gsr_device.h"
 #include "gsr_sort.h"

@@ -13,9 +13,7 @@
 
 #define GSR_WAVE 64
 #define GSR_TILE_PIX (GSR_BLOCK_X * GSR_BLOCK_Y)
-#define GSR_SORT_LDS_KEYS 8192   // 64 KiB of uint64 keys per workgroup in the tile sort
-#define GSR_SORT_XL_KEYS 16384  // 128 KiB of LDS, 16 keys per thread; beyond this the sort runs in global memory
-#define GSR_SORT_SMALL_KEYS 2048 // tiles up to this many entries take the 256-thread / 16 KiB class
+#define GSR_SORT_SMALL_KEYS 2048 // depth buckets up to this many entries are sorted in registers by 256 threads / 16 KiB of LDS (gsr_sort.h)
 #define GSR_ACC_STRIDE 16        // floats per splat in the backward accumulator: nine sums in a 64-byte line of their own (an atomic burst never straddles two lines)
 #define GSR_ACC64_STRIDE 10      // int64 per splat in the deterministic mode's fixed-point accumulator (9 sums + pad, 80 B)
 #define GSR_FIXED_BITS 58        // fixed point: a partial p of splat s is added as llrint(p * 2^(GSR_FIXED_BITS - e_s - e_g)) with
@@ -24,7 +22,7 @@
                                  // whole sum, so the only headroom needed is for what it leaves out (colours above 8/3): 5 bits below 2^63.
                                  // Resolution 2^-58 of the bound: a screen-filling splat's 10^5 partials, whose sum is ~10^-6 of its bound,
                                  // still come out at 10^-8 relative (at 46 bits the 3300 x 3300 test scene was off by 3e-3).
-#define GSR_LDS_HIST_TILES 40960 // 160 KB of LDS / 4 B: the largest tile grid k_count / k_scatter privatise
+#define GSR_LDS_HIST_TILES 40960 // 160 KB of LDS / 4 B: histogram words a workgroup of the rank path's chunked passes can privatise
 #define GSR_RANK_MAX_BUCKETS 4096 // depth buckets of the rank path (16 KB of LDS beside the tile histogram)
 #define GSR_RANK_HIST_TILES (GSR_LDS_HIST_TILES - GSR_RANK_MAX_BUCKETS)   // the largest grid of tile CORNERS, (gx+1)(gy+1), k_rcount / k_rscatter privatise
 #define GSR_RANK_BANDS 24          // frames beyond GSR_RANK_MAX_SPLATS: horizontal bands of tile rows with a depth rank of their own (<= this many)
@@ -54,7 +52,7 @@ struct Settings {  // by-value kernel argument: scalars + the four device pointe
     int exact_scale_grad;
     int forward_only;
     int deterministic;
-    int fast_blend;      // EFFECTIVE fast mode of this frame (gsr_api.hip: off with `deterministic` and on the per-tile sort path)
+    int fast_blend;      // EFFECTIVE fast mode of this frame (gsr_api.hip: off with `deterministic`)
     const float* __restrict__ bg;
     const float* __restrict__ viewmatrix;
     const float* __restrict__ projmatrix;
@@ -298,39 +296,6 @@ __device__ __forceinline__ uint32_t quadrant_mask_of(const Span& s, float ox, fl
         }
     }
     return s.mode == 1 ? 15u : (s.mode == 2 ? 0u : m);
-}
-__device__ __forceinline__ uint32_t quadrant_mask(float2 p, float4 co, float ox, float oy)
-{
-    return quadrant_mask_of(span_of(reach_of(p.x, p.y, co.x, co.y, co.z, co.w)), ox, oy);
-}
-
-template <typename F>
-__device__ __forceinline__ void for_each_tile(int minx, int miny, int maxx, int maxy, uint32_t n, int gx, F f,
-                                              uint32_t payload0, uint32_t payload1)
-{
-    constexpr uint32_t SMALL = 16;
-    if (n > 0 && n <= SMALL) {
-        for (int y = miny; y < maxy; ++y)
-            for (int x = minx; x < maxx; ++x) f((uint32_t)(y * gx + x), payload0, payload1);
-    }
-    uint64_t big = __ballot(n > SMALL);
-    const int lane = lane_id();
-    while (big) {
-        const int src = __builtin_ctzll(big);
-        big &= big - 1;
-        const int bminx = __builtin_amdgcn_readlane(minx, src);
-        const int bminy = __builtin_amdgcn_readlane(miny, src);
-        const int bmaxx = __builtin_amdgcn_readlane(maxx, src);
-        const uint32_t bn = (uint32_t)__builtin_amdgcn_readlane((int)n, src);
-        const uint32_t p0 = (uint32_t)__builtin_amdgcn_readlane((int)payload0, src);
-        const uint32_t p1 = (uint32_t)__builtin_amdgcn_readlane((int)payload1, src);
-        const uint32_t w = (uint32_t)(bmaxx - bminx);
-        for (uint32_t k = (uint32_t)lane; k < bn; k += GSR_WAVE) {
-            const uint32_t y = (uint32_t)bminy + k / w;
-            const uint32_t x = (uint32_t)bminx + k % w;
-            f(y * (uint32_t)gx + x, p0, p1);
-        }
-    }
 }
 
 // ---- SH rows staged through LDS -------------------------------------------------------------------
@@ -588,9 +553,9 @@ struct PreprocessArgs {
     float* __restrict__ shjac;            // [9][sh_jac_stride(P)] d colour / d view direction of the visible splats, or null (sh_jac_stashed)
     uint32_t* __restrict__ tile_count;    // [tiles] zeroed here (the binning histogram of this frame)
     uint32_t* __restrict__ units;         // the GSR_UNIT_LISTS counters of GsrImageLayout.units are zeroed here (k_render<true> appends, k_render_bwd_rp consumes)
-    unsigned long long* __restrict__ rect_total;   // zeroed here; k_count sums tiles_touched into it
+    unsigned long long* __restrict__ rect_total;   // zeroed here; k_rcount sums tiles_touched into it
     int tiles;
-    // production binning (gsr_binning.hip); brec == nullptr on the per-tile sort path
+    // production binning (gsr_binning.hip); brec == nullptr on the rank path
     float4* __restrict__ brec;            // [P][3] binning record
     BinHeader* __restrict__ hdr;          // zeroed by the API before this kernel; statistics accumulated here
     uint32_t* __restrict__ bcount;        // [nb] depth-bucket histogram, zeroed here
@@ -636,19 +601,6 @@ struct PreBwdArgs {
 
 template <bool STASH>   // STASH: writes GsrGeomLayout.shjac (a.shjac != nullptr)
 __global__ void k_preprocess(Settings s, PreprocessArgs a);
-__global__ void k_tile_scan(int tiles, const uint32_t* tile_count, uint32_t* tile_start, uint32_t* tile_cursor, uint2* ranges,
-                            uint32_t* tile_order, unsigned long long* total_dev, unsigned long long* mailbox, unsigned long long seq, unsigned long long post_capacity);
-template <bool CULL>
-__global__ void k_count(int P, int gx, int tiles, const ushort4* rect, const uint32_t* tiles_touched, const float4* grec, uint32_t* tile_count,
-                        unsigned long long* rect_total, uint32_t* block_hist);
-template <bool CULL>
-__global__ void k_scatter(int P, int gx, int tiles, const float* depths, const ushort4* rect, const uint32_t* tiles_touched, const float4* grec,
-                          const uint32_t* tile_start, uint32_t* tile_cursor, unsigned long long* keys,
-                          unsigned long long capacity, const unsigned long long* total_dev, const uint32_t* block_hist);
-template <int KEYS, int THREADS>
-__global__ void k_tile_sort(uint32_t n_lo, uint32_t n_hi, int gx, const uint32_t* tile_order, const uint32_t* tile_count, const uint32_t* tile_start, unsigned long long* keys,
-                            uint32_t* point_list, uint32_t* qlist, uint32_t* qpos, uint32_t* qcount, uint32_t* qstart, const float4* grec,
-                            unsigned long long capacity, const unsigned long long* total_dev);
 template <bool FAST, bool INFER>   // INFER: forward_only frames (no last-contributor bookkeeping)
 __global__ void k_render(Settings s, const uint32_t* tile_order, const uint32_t* qstart, const uint32_t* qcount, const float4* grec,
                          const uint32_t* qpos, const uint32_t* qlist, float* final_T,
@@ -658,12 +610,12 @@ __global__ void k_render(Settings s, const uint32_t* tile_order, const uint32_t*
 __host__ __device__ inline size_t unit_list_cap(size_t tiles) { return (4 * tiles + GSR_UNIT_LISTS - 1) / GSR_UNIT_LISTS * (size_t)GSR_BWD_SEGMENTS; }
 __host__ __device__ inline size_t unit_lists_words(size_t tiles) { return (size_t)32 * GSR_UNIT_LISTS + (size_t)GSR_UNIT_LISTS * unit_list_cap(tiles); }
 __global__ void k_mark_visible(int P, const float* means3D, const float* vm, uint8_t* present);
-template <bool DET, bool FAST>
+template <bool DET>   // DET: fixed-point sums (GsrSettings.deterministic); the exact blend's backward either way
 __global__ void k_render_bwd(Settings s, const uint32_t* tile_order, const uint32_t* qstart, const uint32_t* qcount, const float4* grec,
                              const uint32_t* qpos, const float* final_T,
                              const uint32_t* n_contrib_q, const float* dL_dpix, float* acc, const float* c_final, const float4* ck, int tiles,
                              long long* acc64, const uint32_t* gmax, unsigned long long capacity, const unsigned long long* total_dev);
-template <int WPB>   // waves per workgroup (they share nothing; the LDS tables are per wave)
+// the fast blend's backward: one wave per workgroup
 __global__ void k_render_bwd_rp(Settings s, const uint32_t* qstart, const uint32_t* qcount, const float4* grec,
                                 const uint32_t* qpos, const float* final_T, const uint32_t* n_contrib_q, const float* dL_dpix, float* acc,
                                 const float* c_final, const float4* ck, int tiles, unsigned long long capacity, const unsigned long long* total_dev,

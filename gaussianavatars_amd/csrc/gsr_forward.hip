@@ -2,14 +2,10 @@
 //
 // Pipeline (one frame):
 //   k_preprocess   per splat : project, EWA cov2D, conic, radius, tile rect, SH->RGB
-//   k_count        <=256 WGs : tile histogram of a chunk of splats in LDS, non-empty bins -> L2 atomics
-//   k_tile_scan    1 block   : exclusive scan of the per-tile counts -> tile_start / ranges / I, posts I to the
-//                              host mailbox, and lists the tiles heaviest-first for the per-tile kernels
-//   k_scatter      same WGs  : drops (depth bits << 32 | splat) into its tiles' segments (LDS slot allocation)
-//   k_tile_sort    per tile  : register/cross-lane bitonic sort of the segment by (depth, splat) == the order a
-//                              stable radix sort of (tile << 32 | depth) produces; emits, per 8x8 quadrant, a stream
-//                              of splat indices culled with the exact {alpha >= 1/255} ellipse (and the
-//                              reference-format sorted keys / point list in the parity modes)
+//   (binning)      gsr_rank.hip (per-tile ordering by depth rank) or gsr_binning.hip (depth-ordered scatter): per 8x8
+//                              quadrant, a stream of splat indices in (depth, splat) order, culled with the exact
+//                              {alpha >= 1/255} ellipse (and the reference-format sorted keys / point list in the
+//                              parity modes)
 //   k_render       per quadrant : one wave x 8x8 pixels; the wave gathers its quadrant's stream 60 records at a time into
 //                              its own LDS stage, a chunk ahead, walks them with broadcast LDS reads (no barriers) and
 //                              composites front to back
@@ -42,7 +38,7 @@ __global__ __launch_bounds__(256) void k_preprocess(Settings s, PreprocessArgs a
         // the backward's work lists start empty (k_render<true> appends): the image state is a fresh, uninitialised allocation per forward
         if (i < GSR_UNIT_LISTS) a.units[32 * i] = 0u;
     } else {
-        // this frame's tile histogram starts at zero (k_count runs after this kernel)
+        // this frame's tile histogram starts at zero (k_rcount runs after this kernel)
         for (int t = i; t < a.tiles; t += (int)(gridDim.x * blockDim.x)) a.tile_count[t] = 0u;
         if (i < GSR_UNIT_LISTS) a.units[32 * i] = 0u;   // the backward's work lists start empty (k_render<true> appends)
         if (i == 0) *a.rect_total = 0ull;
@@ -427,418 +423,6 @@ template __global__ void k_preprocess<false>(Settings, PreprocessArgs);
 template __global__ void k_preprocess<true>(Settings, PreprocessArgs);
 
 // ------------------------------------------------------------------------------------------
-// k_count: instances per tile.  Each workgroup owns a contiguous chunk of splats and histograms
-// their tile rects in LDS (ds_add, no return); only the non-empty bins go to the global counters,
-// so a hot tile sees one L2 atomic per workgroup instead of one per instance.
-// ------------------------------------------------------------------------------------------
-template <bool CULL>
-__global__ __launch_bounds__(256) void k_count(int P, int gx, int tiles, const ushort4* __restrict__ rect,
-                                                const uint32_t* __restrict__ tiles_touched, const float4* __restrict__ grec,
-                                                uint32_t* __restrict__ tile_count, unsigned long long* __restrict__ rect_total,
-                                                uint32_t* __restrict__ block_hist)
-{
-    extern __shared__ uint32_t hist[];
-    __shared__ unsigned long long rect_sum[4];
-    const int tid = threadIdx.x;
-    const bool direct = tiles > GSR_LDS_HIST_TILES;   // tile grid too large for an LDS histogram: count in L2 (slow path)
-    if (!direct) {
-        for (int t = tid; t < tiles; t += 256) hist[t] = 0u;
-        __syncthreads();
-    }
-    const int chunk = ((P + (int)gridDim.x - 1) / (int)gridDim.x + 255) / 256 * 256;
-    const int begin = blockIdx.x * chunk;
-    const int end = min(P, begin + chunk);
-    unsigned long long touched = 0;
-    for (int base = begin; base < end; base += 256) {
-        const int i = base + tid;
-        uint32_t n = 0;
-        int minx = 0, miny = 0, maxx = 0, maxy = 0;
-        if (i < end) {
-            n = tiles_touched[i];
-            touched += n;
-            const ushort4 r = rect[i];
-            minx = r.x; miny = r.y; maxx = r.z; maxy = r.w;
-            if (CULL && n) {
-                const float4 g0 = grec[3 * (size_t)i], g1 = grec[3 * (size_t)i + 1];
-                snug_rect(reach_of(g0.x, g0.y, g0.z, g0.w, g1.x, g1.y), minx, miny, maxx, maxy, n);
-            }
-        }
-        if (direct)
-            for_each_tile(minx, miny, maxx, maxy, n, gx, [=](uint32_t tile, uint32_t, uint32_t) { atomicAdd(&tile_count[tile], 1u); }, 0u, 0u);
-        else
-            for_each_tile(minx, miny, maxx, maxy, n, gx, [](uint32_t tile, uint32_t, uint32_t) { atomicAdd(&hist[tile], 1u); }, 0u, 0u);
-    }
-    // the rect-based instance count (the reference's num_rendered) is kept beside the culled one: sum of tiles_touched
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) touched += __shfl_xor(touched, d, 64);
-    if ((tid & 63) == 0) rect_sum[tid >> 6] = touched;
-    __syncthreads();
-    if (tid == 0) atomicAdd(rect_total, rect_sum[0] + rect_sum[1] + rect_sum[2] + rect_sum[3]);
-    if (direct) return;
-    uint32_t* __restrict__ mine = block_hist + (size_t)blockIdx.x * tiles;   // kept for k_scatter (same chunk, same histogram)
-    for (int t = tid; t < tiles; t += 256) {
-        const uint32_t v = hist[t];
-        mine[t] = v;
-        if (v) atomicAdd(&tile_count[t], v);
-    }
-}
-template __global__ void k_count<false>(int, int, int, const ushort4*, const uint32_t*, const float4*, uint32_t*, unsigned long long*, uint32_t*);
-template __global__ void k_count<true>(int, int, int, const ushort4*, const uint32_t*, const float4*, uint32_t*, unsigned long long*, uint32_t*);
-
-// ------------------------------------------------------------------------------------------
-// k_tile_scan: exclusive scan over the tile counters (single workgroup, 1024 threads)
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void k_tile_scan(int tiles, const uint32_t* __restrict__ tile_count,
-                                                     uint32_t* __restrict__ tile_start, uint32_t* __restrict__ tile_cursor,
-                                                     uint2* __restrict__ ranges, uint32_t* __restrict__ tile_order,
-                                                     unsigned long long* __restrict__ total_dev, unsigned long long* mailbox,
-                                                     unsigned long long seq, unsigned long long post_capacity)
-{
-    __shared__ uint32_t wave_tot[16];
-    __shared__ unsigned long long carry_s;
-    __shared__ uint32_t bucket[34];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
-    unsigned long long grand = 0;
-    for (int base = 0; base < tiles; base += 1024) {
-        const int t = base + tid;
-        const uint32_t v = (t < tiles) ? tile_count[t] : 0u;
-        // wave inclusive scan
-        uint32_t incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += up;
-        }
-        if (lane == 63) wave_tot[wid] = incl;
-        __syncthreads();
-        uint32_t wave_off = 0;
-        for (int w = 0; w < wid; ++w) wave_off += wave_tot[w];
-        const unsigned long long carry = carry_s;
-        const uint32_t excl = (uint32_t)carry + wave_off + incl - v;   // offsets are 32-bit like upstream's
-        if (t < tiles) {
-            tile_start[t] = excl;
-            tile_cursor[t] = 0u;
-            ranges[t] = v ? make_uint2(excl, excl + v) : make_uint2(0u, 0u);
-        }
-        __syncthreads();
-        if (tid == 1023) carry_s = carry + wave_off + incl;   // 64-bit running total: a frame past 2^32 instances is reported, not wrapped
-        __syncthreads();
-    }
-    if (tid == 0) {
-        grand = carry_s;
-        *total_dev = grand;
-        // post (seq, I) to the host: one 8-byte system-scope store into mapped pinned memory
-        __hip_atomic_store(mailbox, (seq << 40) | (grand & 0xFFFFFFFFFFull), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        // deferred count (post_capacity = the binning capacity, else ~0): a frame that does not fit leaves a STICKY mark in the slot's second
-        // word -- later frames overwrite the count above, nothing but the host clears this one (gsr_count_slot_overflow)
-        if (grand > post_capacity) __hip_atomic_store(mailbox + GSR_COUNT_SLOTS, grand, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    // ---- heavy-first launch order for the per-tile kernels --------------------------------------------
-    // Per-tile work is heavy-tailed (a few tiles hold thousands of instances).  The dispatcher hands out
-    // workgroups in index order, so listing tiles by descending instance count (bucketed by log2, one
-    // counting-sort pass in LDS) lets the light tiles fill in behind the heavy ones instead of a heavy
-    // tile starting late on an already busy CU.  Pure scheduling: results do not depend on the order.
-    if (tid < 34) bucket[tid] = 0u;
-    __syncthreads();
-    auto bucket_of = [](uint32_t c) { return c ? 32u - (uint32_t)(31 - __builtin_clz(c)) - 1u : 32u; };   // big counts first, empty last
-    for (int t = tid; t < tiles; t += 1024) atomicAdd(&bucket[bucket_of(tile_count[t])], 1u);
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t run = 0;
-        for (int b = 0; b < 33; ++b) { const uint32_t c = bucket[b]; bucket[b] = run; run += c; }
-    }
-    __syncthreads();
-    for (int t = tid; t < tiles; t += 1024) tile_order[atomicAdd(&bucket[bucket_of(tile_count[t])], 1u)] = (uint32_t)t;
-}
-
-// ------------------------------------------------------------------------------------------
-// k_scatter: one (depth bits << 32 | splat) entry into every touched tile's segment.  Same chunking
-// as k_count, whose per-workgroup histogram it re-uses: the workgroup reserves one contiguous sub-range per
-// touched tile with a single returning L2 atomic, then hands out slots with returning LDS atomics.
-// Order inside a tile segment is arbitrary here; k_tile_sort fixes it.
-// ------------------------------------------------------------------------------------------
-template <bool CULL>
-__global__ __launch_bounds__(256) void k_scatter(int P, int gx, int tiles, const float* __restrict__ depths,
-                                                  const ushort4* __restrict__ rect, const uint32_t* __restrict__ tiles_touched,
-                                                  const float4* __restrict__ grec, const uint32_t* __restrict__ tile_start, uint32_t* __restrict__ tile_cursor,
-                                                  unsigned long long* __restrict__ keys, unsigned long long capacity,
-                                                  const unsigned long long* __restrict__ total_dev, const uint32_t* __restrict__ block_hist)
-{
-    extern __shared__ uint32_t hist[];
-    if (*total_dev > capacity) return;  // the host will grow the buffer and replay the frame
-    const int tid = threadIdx.x;
-    const bool direct = tiles > GSR_LDS_HIST_TILES;
-    const int chunk = ((P + (int)gridDim.x - 1) / (int)gridDim.x + 255) / 256 * 256;
-    const int begin = blockIdx.x * chunk;
-    const int end = min(P, begin + chunk);
-    if (direct) {
-        // slow path for tile grids beyond the LDS histogram: one returning L2 atomic per instance
-        for (int base = begin; base < end; base += 256) {
-            const int i = base + tid;
-            uint32_t n = 0, dbits = 0;
-            int minx = 0, miny = 0, maxx = 0, maxy = 0;
-                if (i < end) {
-                n = tiles_touched[i];
-                const ushort4 r = rect[i];
-                minx = r.x; miny = r.y; maxx = r.z; maxy = r.w;
-                dbits = __float_as_uint(depths[i]);
-                if (CULL && n) {
-                    const float4 g0 = grec[3 * (size_t)i], g1 = grec[3 * (size_t)i + 1];
-                    snug_rect(reach_of(g0.x, g0.y, g0.z, g0.w, g1.x, g1.y), minx, miny, maxx, maxy, n);
-                }
-            }
-            for_each_tile(minx, miny, maxx, maxy, n, gx,
-                          [=](uint32_t tile, uint32_t db, uint32_t idx) {
-                              const uint32_t slot = tile_start[tile] + atomicAdd(&tile_cursor[tile], 1u);
-                              keys[slot] = ((unsigned long long)db << 32) | (unsigned long long)idx;
-                          },
-                          dbits, (uint32_t)i);
-        }
-        return;
-    }
-    // this workgroup's tile histogram was already built by k_count (same chunk): reserve one contiguous sub-range per touched
-    // tile with a single returning L2 atomic
-    const uint32_t* __restrict__ mine = block_hist + (size_t)blockIdx.x * tiles;
-    for (int t = tid; t < tiles; t += 256) {
-        const uint32_t v = mine[t];
-        hist[t] = v ? tile_start[t] + atomicAdd(&tile_cursor[t], v) : 0u;   // first slot of this workgroup in tile t
-    }
-    __syncthreads();
-    for (int base = begin; base < end; base += 256) {
-        const int i = base + tid;
-        uint32_t n = 0, dbits = 0;
-        int minx = 0, miny = 0, maxx = 0, maxy = 0;
-        if (i < end) {
-            n = tiles_touched[i];
-            const ushort4 r = rect[i];
-            minx = r.x; miny = r.y; maxx = r.z; maxy = r.w;
-            if (CULL && n) {
-                const float4 g0 = grec[3 * (size_t)i], g1 = grec[3 * (size_t)i + 1];
-                snug_rect(reach_of(g0.x, g0.y, g0.z, g0.w, g1.x, g1.y), minx, miny, maxx, maxy, n);
-            }
-            dbits = __float_as_uint(depths[i]);
-        }
-        for_each_tile(minx, miny, maxx, maxy, n, gx,
-                      [=](uint32_t tile, uint32_t db, uint32_t idx) {
-                          const uint32_t slot = atomicAdd(&hist[tile], 1u);
-                          keys[slot] = ((unsigned long long)db << 32) | (unsigned long long)idx;
-                      },
-                      dbits, (uint32_t)i);
-    }
-}
-template __global__ void k_scatter<false>(int, int, int, const float*, const ushort4*, const uint32_t*, const float4*, const uint32_t*, uint32_t*,
-                                          unsigned long long*, unsigned long long, const unsigned long long*, const uint32_t*);
-template __global__ void k_scatter<true>(int, int, int, const float*, const ushort4*, const uint32_t*, const float4*, const uint32_t*, uint32_t*,
-                                         unsigned long long*, unsigned long long, const unsigned long long*, const uint32_t*);
-
-// Epilogue for the register-sorted classes.  The sorted keys are first laid out in LDS in natural order so
-// that thread t handles entries c*THREADS + t (c = 0..7): consecutive lanes own consecutive entries and
-// their compacted records land next to each other (coalesced stores).  Membership is one 4-bit mask per
-// entry; the stable compaction into the four quadrant streams uses ballots for the in-wave rank and ONE
-// exclusive scan over the (chunk, wave) counters -- three barriers in total, gathers issued four chunks at a time.
-template <int THREADS, int EPT>
-__device__ __forceinline__ void epilogue_striped(const u64 (&key)[EPT], uint32_t n, uint32_t tile, uint32_t start, float ox, float oy,
-                                                 u64* __restrict__ seg, uint32_t* __restrict__ point_list, uint32_t* __restrict__ qlbase,
-                                                 uint32_t* __restrict__ qpbase, uint32_t* __restrict__ qcount, const float4* __restrict__ grec,
-                                                 u64* __restrict__ sk, uint32_t (*__restrict__ cntw)[EPT * (THREADS / 64) + 1], int tid)
-{
-    constexpr int NW = THREADS / 64, NE = EPT * NW;   // waves, (chunk, wave) counters per quadrant
-    constexpr int PER = (NE + 63) / 64;               // counters per lane in the scan
-    const int lane = tid & 63, wid = tid >> 6;
-#pragma unroll
-    for (int k = 0; k < EPT; ++k) sk[tid * EPT + k] = key[k];
-    __syncthreads();
-    uint32_t msk[EPT], rank[EPT];   // rank: 4 x 8-bit in-wave exclusive ranks (0..63)
-    const u64 tile_hi = (u64)tile << 32;
-    // pass 1: gather the geometry half of each instance's per-splat record (centre, conic, opacity: 32 of its 48 bytes),
-    // evaluate its quadrant mask / in-wave ranks, and write the reference-format lists in the parity modes
-#pragma unroll
-    for (int h = 0; h < EPT / 4; ++h) {
-        float4 g0[4], g1[4];
-        u64 kk[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t i = (uint32_t)(4 * h + k) * THREADS + (uint32_t)tid;
-            kk[k] = i < n ? sk[i] : 0ull;
-            const uint32_t idx = (uint32_t)kk[k];
-            g0[k] = grec[3 * (size_t)idx + 0];
-            g1[k] = grec[3 * (size_t)idx + 1];
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int c = 4 * h + k;
-            const uint32_t i = (uint32_t)c * THREADS + (uint32_t)tid;
-            if (i < n && point_list) {   // the reference-format lists are a parity/debug artefact: nothing downstream reads them
-                seg[i] = tile_hi | (kk[k] >> 32);   // reference-format key: tile id | depth bits
-                point_list[start + i] = (uint32_t)kk[k];
-            }
-            const uint32_t m = i < n ? quadrant_mask(make_float2(g0[k].x, g0[k].y), make_float4(g0[k].z, g0[k].w, g1[k].x, g1[k].y), ox, oy) : 0u;
-            msk[c] = m;
-            uint32_t r = 0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const unsigned long long bal = __ballot((m >> q) & 1u);
-                r |= (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u)) << (8 * q);
-                if (lane == 0) cntw[q][c * NW + wid] = (uint32_t)__builtin_popcountll(bal);
-            }
-            rank[c] = r;
-        }
-    }
-    __syncthreads();
-    // exclusive scan of the NE counters of each quadrant (wave q scans quadrant q; NE <= 128 = 2 per lane)
-    if (wid < 4) {
-        uint32_t a[PER], sum = 0;
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int e = PER * lane + j;
-            a[j] = e < NE ? cntw[wid][e] : 0u;
-            sum += a[j];
-        }
-        uint32_t incl = sum;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = (uint32_t)__builtin_amdgcn_ds_bpermute((lane >= d ? lane - d : lane) << 2, (int)incl);
-            if (lane >= d) incl += up;
-        }
-        uint32_t run = incl - sum;
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int e = PER * lane + j;
-            if (e < NE) cntw[wid][e] = run;
-            run += a[j];
-        }
-        if (lane == 63) cntw[wid][NE] = incl;   // total
-    }
-    __syncthreads();
-    // pass 2: the quadrant streams get the SPLAT INDICES (4 bytes per (instance, quadrant) pair), stable order; in the parity
-    // modes a twin stream keeps each entry's position in the tile list (what the reference's n_contrib counts)
-#pragma unroll
-    for (int c = 0; c < EPT; ++c) {
-        const uint32_t i = (uint32_t)c * THREADS + (uint32_t)tid;
-        const uint32_t m = msk[c];
-        const uint32_t idx = m ? (uint32_t)sk[i] : 0u;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if ((m >> q) & 1u) {
-                const uint32_t pos = cntw[q][c * NW + wid] + ((rank[c] >> (8 * q)) & 0xFFu);
-                qpbase[(size_t)q * n + pos] = idx;
-                if (qlbase) qlbase[(size_t)q * n + pos] = i;
-            }
-        }
-    }
-    if (tid < 4) qcount[4 * tile + tid] = cntw[tid][NE];
-}
-
-// Three size classes share this body: tiles with n_lo < n <= n_hi are handled, the rest exit at once.
-//   small: <= 2048 entries, 256 threads x 8 keys, 16 KiB LDS (many workgroups per CU)
-//   large: <= 8192 entries, 1024 threads x 8 keys, 64 KiB LDS
-//   xl:    <= 16384 entries, 1024 threads x 16 keys, 128 KiB LDS; beyond that chunked sorts + merges in global memory
-template <int KEYS, int THREADS>
-__global__ __launch_bounds__(THREADS) void k_tile_sort(uint32_t n_lo, uint32_t n_hi, int gx, const uint32_t* __restrict__ tile_order,
-                                                        const uint32_t* __restrict__ tile_count,
-                                                    const uint32_t* __restrict__ tile_start, unsigned long long* __restrict__ keys,
-                                                    uint32_t* __restrict__ point_list, uint32_t* __restrict__ qlist,
-                                                    uint32_t* __restrict__ qpos, uint32_t* __restrict__ qcount, uint32_t* __restrict__ qstart,
-                                                    const float4* __restrict__ grec,
-                                                    unsigned long long capacity, const unsigned long long* __restrict__ total_dev)
-{
-    __shared__ unsigned long long skeys[KEYS];
-    __shared__ uint32_t wave_cnt[4][THREADS / 64];   // [quadrant][wave]  (chunked fallback epilogue)
-    constexpr int EPT = KEYS / THREADS;
-    __shared__ uint32_t cntw[4][EPT * (THREADS / 64) + 1];   // [quadrant][(chunk, wave)] + total  (striped epilogue)
-    if (*total_dev > capacity) return;
-    const uint32_t tile = tile_order[blockIdx.x];
-    const uint32_t n = tile_count[tile];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    if (n <= n_lo || n > n_hi) {
-        if (n == 0 && n_lo == 0 && tid < 4) { qcount[4 * tile + tid] = 0u; qstart[4 * tile + tid] = 0u; }
-        return;
-    }
-    const uint32_t start = tile_start[tile];
-    if (tid < 4) qstart[4 * tile + tid] = 4u * start + (uint32_t)tid * n;   // the tile's four n-slot streams
-    unsigned long long* seg = keys + start;
-    const bool in_lds = n <= (uint32_t)KEYS;
-    const float ox = (float)((tile % (uint32_t)gx) * GSR_BLOCK_X), oy = (float)((tile / (uint32_t)gx) * GSR_BLOCK_Y);
-    uint32_t* const qpbase = qpos + (size_t)4 * start;      // the tile's four quadrant streams of splat indices, n slots each
-    uint32_t* const qlbase = qlist ? qlist + (size_t)4 * start : nullptr;   // parity modes: the entries' positions in the tile list
-    if (in_lds) {
-        static_assert(EPT == 8 || EPT == 16, "register sort holds 8 or 16 keys per thread");
-        u64 key[EPT];
-        block_sort_regs<THREADS, EPT>(key, skeys, seg, n, tid);
-        epilogue_striped<THREADS, EPT>(key, n, tile, start, ox, oy, seg, point_list, qlbase, qpbase, qcount, grec, skeys, cntw, tid);
-        return;
-    } else {
-        // more entries than this class holds in LDS: chunked register sorts + global merge passes (scratch: the tile's
-        // still-unwritten quadrant streams, 16 n bytes for n 8-byte keys)
-        oversize_sort<THREADS, EPT>(seg, reinterpret_cast<u64*>(qpbase), skeys, n, tid);
-        __syncthreads();
-    }
-    // ---- epilogue: reference-format keys / point list, and the four 8x8-quadrant record streams --------
-    // A record goes to quadrant q only if the exact ellipse {alpha >= 1/255} of the splat can reach a pixel
-    // centre of q (conservatively padded), i.e. only (record, quadrant) pairs the blend would skip for every
-    // pixel are dropped: the composited result is unchanged, the blend's lists get ~3x shorter.  Order inside
-    // a quadrant stream is the tile order (stable compaction), r2.z keeps the position in the tile list.
-    const unsigned long long tile_hi = (unsigned long long)tile << 32;
-    uint32_t running[4] = {0u, 0u, 0u, 0u};
-    for (uint32_t base = 0; base < n; base += THREADS) {
-        const uint32_t i = base + tid;
-        const bool valid = i < n;
-        bool f[4] = {false, false, false, false};
-        uint32_t idx = 0u;
-        if (valid) {
-            const unsigned long long k = in_lds ? skeys[i] : seg[i];
-            idx = (uint32_t)k;
-            if (point_list) {
-                seg[i] = tile_hi | (k >> 32);
-                point_list[start + i] = idx;
-            }
-            const float4 r0 = grec[3 * (size_t)idx + 0];
-            const float4 r1 = grec[3 * (size_t)idx + 1];
-            const uint32_t m = quadrant_mask(make_float2(r0.x, r0.y), make_float4(r0.z, r0.w, r1.x, r1.y), ox, oy);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) f[q] = (m >> q) & 1u;
-        }
-        uint32_t prefix[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const unsigned long long bal = __ballot(f[q]);
-            prefix[q] = (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-            if (lane == 0) wave_cnt[q][wid] = (uint32_t)__builtin_popcountll(bal);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            uint32_t off = running[q], tot = 0;
-#pragma unroll
-            for (int w = 0; w < THREADS / 64; ++w) {
-                const uint32_t cw = wave_cnt[q][w];
-                if (w < wid) off += cw;
-                tot += cw;
-            }
-            if (f[q]) {
-                qpbase[(size_t)q * n + off + prefix[q]] = idx;
-                if (qlbase) qlbase[(size_t)q * n + off + prefix[q]] = i;
-            }
-            running[q] += tot;
-        }
-        __syncthreads();
-    }
-    if (tid < 4) qcount[4 * tile + tid] = running[tid];
-}
-
-template __global__ void k_tile_sort<GSR_SORT_SMALL_KEYS, 256>(uint32_t, uint32_t, int, const uint32_t*, const uint32_t*, const uint32_t*, unsigned long long*, uint32_t*, uint32_t*,
-                                                                uint32_t*, uint32_t*, uint32_t*, const float4*, unsigned long long,
-                                                                const unsigned long long*);
-template __global__ void k_tile_sort<GSR_SORT_LDS_KEYS, 1024>(uint32_t, uint32_t, int, const uint32_t*, const uint32_t*, const uint32_t*, unsigned long long*, uint32_t*, uint32_t*,
-                                                               uint32_t*, uint32_t*, uint32_t*, const float4*, unsigned long long,
-                                                               const unsigned long long*);
-template __global__ void k_tile_sort<GSR_SORT_XL_KEYS, 1024>(uint32_t, uint32_t, int, const uint32_t*, const uint32_t*, const uint32_t*, unsigned long long*, uint32_t*, uint32_t*,
-                                                              uint32_t*, uint32_t*, uint32_t*, const float4*, unsigned long long,
-                                                              const unsigned long long*);
-
-// ------------------------------------------------------------------------------------------
 // k_render: front-to-back compositing.  Workgroup = ONE wave = one 8x8 quadrant: workgroup 4 p + q
 // blends quadrant (q&1, q>>1) of the 16x16 tile at launch position p and walks that quadrant's
 // record stream.  A tile's four walks share nothing; as four waves of one workgroup the slots of
@@ -903,19 +487,13 @@ __global__ __launch_bounds__(64) void k_render(Settings s, const uint32_t* __res
     // A wave on the critical path retires one instruction per ~6.6 cycles whatever its kind (measured: tools/pmc_kernel.sh,
     // tools/bwd_timeline.py), so the loop is written for INSTRUCTION COUNT, scalar ones included: no per-record bounds
     // tests (full batches take an unmasked body), 32-bit record offsets, no exec-mask branches around the exponential.
-#ifndef GSR_EXP_RB
-#define GSR_EXP_RB 3
-#endif
-    constexpr int RB = GSR_EXP_RB;
-#ifndef GSR_FAST_TAIL_LANES
-#define GSR_FAST_TAIL_LANES 12
-#endif
+    constexpr int RB = 3;
     // switch to record-parallel mode when this few pixels are still open.  Exact walk: the tail's T/C update is serial over the hits (swept
     // 0..16 on the instruction-count build: 2-4 best, 8 costs 10 %, 16 costs 50 % of the kernel).  Fast blend: the tail evaluates a pixel's
     // 60 records with one wave scan (no serial loop), ~75 instructions per (pixel, chunk) against 60 x 42 for the walk, so it takes over
     // much earlier (model on the cfg3 frame, tools/remap_model.py: 31.7 M -> 26.3 M instructions at 8..16 open pixels).
-    constexpr int TAIL_LANES = FAST ? GSR_FAST_TAIL_LANES : 4;
-    struct Rec4 { float a[RB][8]; float cbl[RB]; float hi[RB]; };   // a = (x, y, conic a, conic b, conic c, opacity | fast: log2 opacity, red, green); blue; fast: alpha's upper bound -- in vector registers, read from the wave's LDS stage
+    constexpr int TAIL_LANES = FAST ? 12 : 4;
+    struct Rec4 { float a[RB][8]; float cbl[RB]; };   // a = (x, y, conic a, conic b, conic c, opacity | fast: log2 opacity, red, green); blue -- in vector registers, read from the wave's LDS stage
     // last_q is carried RELATIVE to the walk position (lq = last_q - j0 at the top of an iteration): a hit then stores a small constant,
     // which v_cndmask takes inline -- an absolute index costs a scalar add and a v_mov per record on top of the select
     int lq = 0;
@@ -934,11 +512,7 @@ __global__ __launch_bounds__(64) void k_render(Settings s, const uint32_t* __res
                 // ONE median + ONE comparison (a NaN -- an opacity below 1/255 has L = NaN -- fails it)
                 power = __builtin_fmaf(__builtin_fmaf(R.a[u][3], dy, R.a[u][2] * dx), dx, __builtin_fmaf(R.a[u][4] * dy, dy, R.a[u][5]));
                 const float raw = __builtin_amdgcn_exp2f(power);
-#ifdef GSR_EXP_HI_TEST
-                ok[u] = __builtin_amdgcn_fmed3f(raw, 1.0f / 255.0f, R.hi[u]) == raw;
-#else
                 ok[u] = raw >= 1.0f / 255.0f;   // (NaN fails)
-#endif
                 a = __builtin_amdgcn_fmed3f(raw, 0.0f, 0.99f);   // = min(0.99, raw) for raw >= 0.  (fminf would first canonicalise the exponential's result, one more
                                                                  // instruction; an inline-asm v_min hides the operand from the compiler's hazard recogniser, which has to
                                                                  // put a wait state between a transcendental and the VALU instruction that reads its result: measured, T > 1)
@@ -1031,24 +605,16 @@ __global__ __launch_bounds__(64) void k_render(Settings s, const uint32_t* __res
     // believes they were written at the issue), and nothing else of this wave is in flight on lgkmcnt inside the loop (no scalar
     // loads, no compiler-made LDS access).
     typedef float v4f __attribute__((ext_vector_type(4)));
-#ifdef GSR_EXP_HI_TEST
-    typedef float v2f __attribute__((ext_vector_type(2)));
-    typedef v2f q2_t;   // (blue, alpha's upper bound)
-#define GSR_Q2_READ "ds_read_b64"
-#else
-    typedef float q2_t;   // blue
-#define GSR_Q2_READ "ds_read_b32"
-#endif
-    struct RecV { v4f q0[RB], q1[RB]; q2_t q2[RB]; };
+    struct RecV { v4f q0[RB], q1[RB]; float q2[RB]; };   // q2: blue
     static_assert(RB == 3, "the issue / ready assembly below is written for three records per batch");
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float4*)&stage[0][0], lds1 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float4*)&stage[1][0];
     // `addr`: the LDS byte address of the walk's current double batch (a vector register that only ever gets a constant added);
     // `O`: 0, 1 or 2 batches (BB bytes each) ahead of it, as immediates -- no address arithmetic per batch
     // (a macro: captured variables inside the operand list of an asm in a GENERIC lambda do not compile with this clang)
 #define GSR_ISSUE(ADDR, O, V)                                                                                                                        \
-    asm volatile("ds_read_b128 %0, %14 offset:%15\n\tds_read_b128 %1, %14 offset:%16\n\t" GSR_Q2_READ " %2, %14 offset:%17\n\t"                       \
-                 "ds_read_b128 %3, %14 offset:%18\n\tds_read_b128 %4, %14 offset:%19\n\t" GSR_Q2_READ " %5, %14 offset:%20\n\t"                       \
-                 "ds_read_b128 %6, %14 offset:%21\n\tds_read_b128 %7, %14 offset:%22\n\t" GSR_Q2_READ " %8, %14 offset:%23"                             \
+    asm volatile("ds_read_b128 %0, %14 offset:%15\n\tds_read_b128 %1, %14 offset:%16\n\tds_read_b32 %2, %14 offset:%17\n\t"                           \
+                 "ds_read_b128 %3, %14 offset:%18\n\tds_read_b128 %4, %14 offset:%19\n\tds_read_b32 %5, %14 offset:%20\n\t"                           \
+                 "ds_read_b128 %6, %14 offset:%21\n\tds_read_b128 %7, %14 offset:%22\n\tds_read_b32 %8, %14 offset:%23"                               \
                  : "=&v"(V.q0[0]), "=&v"(V.q1[0]), "=&v"(V.q2[0]), "=&v"(V.q0[1]), "=&v"(V.q1[1]), "=&v"(V.q2[1]), "=&v"(V.q0[2]),              \
                    "=&v"(V.q1[2]), "=&v"(V.q2[2]), /* the blend state as pass-through operands: the reads are issued BEHIND everything the */    \
                    /* previous blend computes (its instructions are free to move otherwise, and below this statement they need the old */       \
@@ -1068,11 +634,7 @@ __global__ __launch_bounds__(64) void k_render(Settings s, const uint32_t* __res
         for (int u = 0; u < RB; ++u) {
             R.a[u][0] = V.q0[u].x; R.a[u][1] = V.q0[u].y; R.a[u][2] = V.q0[u].z; R.a[u][3] = V.q0[u].w;
             R.a[u][4] = V.q1[u].x; R.a[u][5] = V.q1[u].y; R.a[u][6] = V.q1[u].z; R.a[u][7] = V.q1[u].w;
-#ifdef GSR_EXP_HI_TEST
-            R.cbl[u] = V.q2[u].x; R.hi[u] = V.q2[u].y;
-#else
-            R.cbl[u] = V.q2[u]; R.hi[u] = 0.0f;
-#endif
+            R.cbl[u] = V.q2[u];
         }
     };
     using Behind9 = std::integral_constant<int, 9>;
@@ -1103,11 +665,7 @@ __global__ __launch_bounds__(64) void k_render(Settings s, const uint32_t* __res
                 const float dx = r0.x - ppx, dy = r0.y - ppy;
                 const float power = __builtin_fmaf(__builtin_fmaf(r0.w, dy, r0.z * dx), dx, __builtin_fmaf(r1.x * dy, dy, r1.y));   // (the walk's expressions)
                 const float raw = __builtin_amdgcn_exp2f(power);
-#ifdef GSR_EXP_HI_TEST
-                ok[e] = valid && __builtin_amdgcn_fmed3f(raw, 1.0f / 255.0f, r2.y) == raw;
-#else
                 ok[e] = valid && raw >= 1.0f / 255.0f;
-#endif
                 const float a = __builtin_amdgcn_fmed3f(raw, 0.0f, 0.99f);
                 am[e] = ok[e] ? a : 0.0f;
                 prod[e] = 1.0f - am[e];

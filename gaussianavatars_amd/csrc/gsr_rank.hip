@@ -5,7 +5,7 @@
 // (depth, index) order restricted to the tile, so here the splats are ranked once (P keys, 17x fewer than instances) and a
 // tile orders its instances by setting bit `rank` in an LDS bitmap and reading the bitmap back in order -- no comparisons:
 //
-//   k_rcount    per chunk  : tile-instance histogram (as round 1's k_count) + depth-bucket histogram of the binned splats,
+//   k_rcount    per chunk  : tile-instance histogram + depth-bucket histogram of the binned splats,
 //                            snug tile rect of every splat kept for the two scatters
 //   k_rdscatter per chunk  : bucket offsets (every workgroup scans the nb counters itself), (depth bits << 32 | splat) into buckets
 //               + 1 WG     : exclusive scan of the tile counters, heavy-first tile order, instance count posted to the host
@@ -314,7 +314,11 @@ __device__ __forceinline__ void tile_scan_256(int tiles, const uint32_t* __restr
         // word -- later frames overwrite the count above, nothing but the host clears this one (gsr_count_slot_overflow)
         if (grand > post_capacity) __hip_atomic_store(mailbox + GSR_COUNT_SLOTS, grand, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    // heavy-first launch order for the per-tile kernels (pure scheduling, see round 1's k_tile_scan)
+    // ---- heavy-first launch order for the per-tile kernels --------------------------------------------
+    // Per-tile work is heavy-tailed (a few tiles hold thousands of instances).  The dispatcher hands out
+    // workgroups in index order, so listing tiles by descending instance count (bucketed by log2, one
+    // counting-sort pass in LDS) lets the light tiles fill in behind the heavy ones instead of a heavy
+    // tile starting late on an already busy CU.  Pure scheduling: results do not depend on the order.
     if (tid < 34) bucket[tid] = 0u;
     __syncthreads();
     auto bucket_of = [](uint32_t c) { return c ? 32u - (uint32_t)(31 - __builtin_clz(c)) - 1u : 32u; };   // big counts first, empty last
@@ -421,7 +425,7 @@ __device__ __forceinline__ void tile_scan_wide(const TileScanArgs& ts)
         }
     }
     __syncthreads();
-    // heavy-first launch order for the per-tile kernels (pure scheduling, see round 1's k_tile_scan)
+    // heavy-first launch order for the per-tile kernels (pure scheduling, as explained in the one-workgroup scan above)
 #pragma unroll
     for (int k = 0; k < TS_PER; ++k) {
         const int t = w0 + 64 * k + lane;
@@ -732,12 +736,8 @@ __device__ __forceinline__ void rscatter_body(int P, int gx, int tiles, BandTabl
             const uint32_t m = quadrant_mask_of(b, (float)(x * GSR_BLOCK_X), (float)(y * GSR_BLOCK_Y));
             // tile grids beyond the LDS histogram: one returning L2 atomic per instance
             const uint32_t slot = direct ? tile_start[tile] + atomicAdd(&tile_cursor[tile], 1u) : atomicAdd(&hist[tile], 1u);
-#ifdef GSR_EXP_RSCATTER_NOSTORE   // timing experiment: everything but the store (the condition keeps the rank, the mask and the slot live; no frame meets it)
-            if (brk == 0xFFFFFFF0u && m == 15u && bidx == 0x0FFFFFFFu) ranks[slot] = make_uint2(brk, bidx);
-#else
             if (LEAN) lean[slot] = bidx | (m << GSR_RANK_IDX_BITS);
             else ranks[slot] = make_uint2(brk, bidx | (m << GSR_RANK_IDX_BITS));
-#endif
         });
     }
 }

@@ -1,5 +1,5 @@
-// gsr_sort.h -- register-resident bitonic block sort of 64-bit keys (shared by the per-tile sort of the parity modes and the
-// per-bucket depth sort of the production binning).
+// gsr_sort.h -- register-resident bitonic block sort of 64-bit keys (the per-bucket depth sorts of both binnings:
+// gsr_binning.hip k_dsort, gsr_rank.hip k_rdsort / k_rsort_rscatter).
 #pragma once
 #include "gsr_device.h"
 
@@ -115,10 +115,10 @@ __device__ __forceinline__ void block_sort_regs(u64 (&key)[EPT], u64* __restrict
 }
 
 // ------------------------------------------------------------------------------------------
-// Oversize tiles (more entries than the LDS class holds): sort KEYS-sized chunks with the register sort,
+// Oversize buckets (more entries than the LDS class holds): sort KEYS-sized chunks with the register sort,
 // then merge the runs pairwise in global memory (merge path: every thread binary-searches its diagonal
-// and merges a private output slice).  `tmp` is scratch of at least n keys (the tile's still-unused
-// quadrant-record region); the sorted result always ends in seg[0..n).  Keys are unique per tile.
+// and merges a private output slice).  `tmp` is scratch of at least n keys; the sorted result always
+// ends in seg[0..n).  Keys are unique per bucket.
 // ------------------------------------------------------------------------------------------
 template <int THREADS, int EPT>
 __device__ __forceinline__ void oversize_sort(u64* __restrict__ seg, u64* __restrict__ tmp, u64* __restrict__ sk, uint32_t n, int tid)

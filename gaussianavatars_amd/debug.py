@@ -64,12 +64,12 @@ def _forward_state(rs, means3D, shs, colors_precomp, opacities, scales, rotation
 
     lib.gsr_binning_layout(cap, W, H, P, int(_R.get_tile_culling()), C.byref(bl))
     prod = bl.path == 1
-    lists = int(_R.get_tile_culling()) in (0, 2) or bl.path == 2   # the reference-format key / point lists were written
+    lists = int(_R.get_tile_culling()) in (0, 2)   # the reference-format key / point lists were written
     lib.gsr_image_layout(W, H, C.byref(il))
     tiles = ((W + 15) // 16) * ((H + 15) // 16)
     f32, u32, i16 = torch.float32, torch.int32, torch.int16
     rec = _view(geom, gl.grec, 12 * P, f32).view(P, 12)
-    fast = bool(ctx.fast_blend) and not ctx.deterministic and bl.path != 2   # gsr_api.hip: fast_effective
+    fast = bool(ctx.fast_blend) and not ctx.deterministic   # gsr_api.hip: fast_effective
     out = dict(
         color=color, radii=radii, num_rendered=I, capacity=cap,
         rect_instances=int(_view(binning, 8, 1, torch.int64).item()),

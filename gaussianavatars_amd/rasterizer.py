@@ -92,9 +92,7 @@ _fast_blend = int(os.environ.get("GSR_FAST_BLEND", "1"))
 
 
 def set_fast_blend(enabled) -> int:
-    """Process-wide switch; returns the previous value.  True / False (1 / 0) select the fast / exact kernels; the raw integer 2 (the A/B
-    mode of include/gsr.h: fast forward with the pixel-parallel fast backward) is kept as it is, so a save / restore pair
-    `prev = set_fast_blend(x); ...; set_fast_blend(prev)` restores every mode."""
+    """Process-wide switch; returns the previous value.  True / False (any non-zero value / 0) select the fast / exact kernels."""
     global _fast_blend
     prev, _fast_blend = _fast_blend, int(enabled)
     return prev
@@ -497,7 +495,9 @@ def _binning_layout(lib, cap, W, H, P, mode):
     hit = _layout_cache.get(key)
     if hit is None:
         hit = _lib.GsrBinningLayout()
-        lib.gsr_binning_layout(cap, W, H, P, mode, C.byref(hit))
+        rc = lib.gsr_binning_layout(cap, W, H, P, mode, C.byref(hit))
+        if rc != 0:   # (a tile_culling the library does not have: nothing was laid out)
+            raise RuntimeError(f"gsr_binning_layout failed ({rc}): {_lib.gsr_error()}")
         if len(_layout_cache) > 64:
             _layout_cache.clear()
         _layout_cache[key] = hit

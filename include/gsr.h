@@ -74,9 +74,9 @@ typedef struct GsrSettings {
                                  2: culled, lists written (what the subsequence parity tests inspect);
                                  3: as 1 but always on the rank path (tiles ordered through bitmaps of global depth ranks: the default
                                     wherever the depth-ordered scatter does not apply), 4: as 1 but on the depth-ordered scatter whenever it
-                                    applies, whatever the splat count, 5: as 1 but on round 1's per-tile bitonic sort (A/B of the three
-                                    binnings, tests), 6: as 3 with the per-band ranks of large frames at any splat count (tests).
-                                    The binning path of a call is GsrBinningLayout.path.                                       */
+                                    applies, whatever the splat count, 6: as 3 with the per-band ranks of large frames at any splat
+                                    count (tests).  The binning path of a call is GsrBinningLayout.path.  Any other value -- 5, which used
+                                    to select a per-tile bitonic sort, included -- is GSR_E_ARG.                                */
     int32_t forward_only;     /* !=0: no backward will follow this forward (inference, torch.no_grad): the forward skips zero-filling
                                  the backward's per-splat accumulators (48 B per visible splat) and writing what only the backward reads
                                  (GsrGeomLayout.cov3D, clamped, shjac; rect on the rank path; round 4: the image state as well -- final_T,
@@ -112,8 +112,7 @@ typedef struct GsrSettings {
                                  the image agrees with the exact mode to ~1e-6 except where a record's alpha sits within an ulp of 1/255 or a
                                  pixel's transmittance within an ulp of 1e-4 (the record is then taken on one side and skipped on the other: a
                                  difference bounded by 1/255 resp. 1e-4 per such pixel; tests/test_fast_blend_gpu.py counts them).  Same value in
-                                 the forward and the backward call of a frame.  Ignored (exact kernels) with `deterministic` and on the per-tile
-                                 sort path (tile_culling 5), whose binning reads the conic from the record.                         */
+                                 the forward and the backward call of a frame.  Ignored (exact kernels) with `deterministic`.          */
 } GsrSettings;
 
 /* Byte offsets of the arrays inside the three opaque state buffers.  The state buffers play the
@@ -206,7 +205,7 @@ typedef struct GsrBinningLayout {
     size_t tdesc;       /* uint32 [tiles][4] (tile, entries, first entry, 0) in launch order (heaviest tiles first)                       */
     size_t obs;         /* uint32 [P][2] bands only: (splat, first band | last band << 8) of the binned splats in depth order         */
     size_t bandcnt;     /* uint32 [nbands][ceil(P/256)] bands only: splats of band b before each run of 256 consecutive depth ranks  */
-    size_t path;        /* 0: rank path, 1: depth-ordered scatter, 2: round 1's per-tile sort (see gsr_binning_layout)       */
+    size_t path;        /* 0: rank path, 1: depth-ordered scatter (see gsr_binning_layout)                               */
     size_t chunks;      /* production: number of chunks (waves) of the ordered walk                                */
     size_t nb;          /* production: number of depth buckets                                                     */
     size_t nbands;      /* rank path: 1 up to 262144 splats; beyond, the tile rows are cut into this many bands (<= 24) ...  */
@@ -257,8 +256,9 @@ int gsr_geom_layout(int32_t P, GsrGeomLayout* out);
  * every tile ordered through an LDS bitmap of ranks; beyond 262144 splats the ranks are taken per band of tile rows so that a
  * band's ranks still fit the bitmap -- GsrBinningLayout.nbands / band_rows); 1 = the
  * depth-ordered scatter, taken by production (tile_culling 1) beyond 262144 splats when the grid has at most 16384 quadrants,
- * P / chunks <= 255 and the chunk-prefix table stays below 1 GiB; 2 = round 1's per-tile bitonic sort (tile_culling 5 only).
- * `capacity` counts the instances the path produces: tile instances on paths 0 and 2, quadrant-stream entries on path 1.   */
+ * P / chunks <= 255 and the chunk-prefix table stays below 1 GiB.
+ * `capacity` counts the instances the path produces: tile instances on path 0, quadrant-stream entries on path 1.
+ * A tile_culling outside 0..4 and 6 is GSR_E_ARG and leaves *out unwritten.                                         */
 int gsr_binning_layout(int64_t capacity, int32_t width, int32_t height, int32_t P, int32_t tile_culling, GsrBinningLayout* out);
 int gsr_image_layout(int32_t width, int32_t height, GsrImageLayout* out);
 

@@ -56,11 +56,8 @@ def test_layouts_are_disjoint_and_aligned():
     assert lib.gsr_binning_layout(cap, 550, 802, P, 3, C.byref(bl)) == 0 and bl.path == 0
     assert bl.keys == bl.point_list and bl.qlist == bl.qpos
     _check([(bl.qpos, 16 * cap), (bl.ranks, 8 * cap), (bl.point_list, 4 * cap), (bl.rank, 4 * P), (bl.srect, 8 * P), (bl.pstat, 8 * nblk)], bl.total)
-    # round 1's per-tile bitonic sort (tile_culling 5, A/B runs)
-    assert lib.gsr_binning_layout(cap, 550, 802, P, 5, C.byref(bl)) == 0 and bl.path == 2
-    segs = [(bl.keys, 8 * cap), (bl.point_list, 4 * cap), (bl.qpos, 16 * cap), (bl.qcount, 16 * tiles), (bl.qstart, 16 * tiles),
-            (bl.ranges, 8 * tiles), (bl.tile_count, 4 * tiles), (bl.tile_start, 4 * tiles), (bl.tile_cursor, 4 * tiles), (bl.tile_order, 4 * tiles)]
-    _check(segs, bl.total)
+    # tile_culling 5 selected the per-tile bitonic sort: removed, and an error rather than another path under the old number
+    assert lib.gsr_binning_layout(cap, 550, 802, P, 5, C.byref(bl)) != 0 and b"per-tile sort was removed" in lib.gsr_last_error()
     # production: depth-ordered scatter into the quadrant streams (capacity counts stream entries)
     capq = 4_000_000
     assert lib.gsr_binning_layout(capq, 550, 802, P, 1, C.byref(bl)) == 0 and bl.path == 0      # up to 262144 splats: the rank path
@@ -74,7 +71,7 @@ def test_layouts_are_disjoint_and_aligned():
             (bl.qhist, bl.chunks * Q), (bl.qprefix, 4 * bl.chunks * Q), (bl.qmask, 16 * P)]
     _check(segs, bl.total)
     # grids beyond 16384 quadrants and splat counts beyond 255 per chunk do not take the scatter: the rank path at any size
-    # (one tile bitmap up to 262144 splats; beyond, ranks per band of tile rows); round 1's per-tile sort only on request (tile_culling 5)
+    # (one tile bitmap up to 262144 splats; beyond, ranks per band of tile rows)
     assert lib.gsr_binning_layout(capq, 1600, 1100, 250_000, 1, C.byref(bl)) == 0 and bl.path == 0 and bl.nbands == 1
     assert lib.gsr_binning_layout(capq, 1600, 1100, 2_000_000, 1, C.byref(bl)) == 0 and bl.path == 0 and bl.nb == 4096
     Pb, tb = 2_000_000, 100 * 69
@@ -84,7 +81,7 @@ def test_layouts_are_disjoint_and_aligned():
     assert lib.gsr_binning_layout(capq, 550, 802, P, 6, C.byref(bl)) == 0 and bl.path == 0     # 6: the bands at any splat count (tests)
     assert bl.band_rows == 3 and bl.nbands == 17 and bl.rank + 16 * P <= bl.rank_over and bl.rank_over + 4 * P * 17 <= bl.srect
     assert lib.gsr_binning_layout(capq, 550, 802, 2_000_000, 1, C.byref(bl)) == 0 and bl.path == 0
-    assert lib.gsr_binning_layout(capq, 1600, 1100, 2_000_000, 5, C.byref(bl)) == 0 and bl.path == 2
+    assert lib.gsr_binning_layout(capq, 1600, 1100, 2_000_000, 5, C.byref(bl)) != 0 and b"per-tile sort was removed" in lib.gsr_last_error()
     _check([(il.final_T, 4 * HW), (il.n_contrib, 4 * HW), (il.n_contrib_q, 4 * HW), (il.c_final, 12 * HW), (il.ck, 144 * HW)], il.total)
     assert lib.gsr_geom_layout(-1, C.byref(gl)) < 0 and b"bad arguments" in lib.gsr_last_error()
 

@@ -357,7 +357,7 @@ def test_production_mode_state(oracle):
                                        t(a["projmatrix"]), deg, t(a["campos"]), False, False)
     args = (t(sp["means3D"]), t(sp["shs"]), None, t(sp["opacities"]), t(sp["scales"]), t(sp["rotations"]), None)
     par = D.forward_state(rs, *args, tile_culling=True)
-    for mode in (1, 3, 4, 5):  # 1: what render() runs (rank path at this size), 3 / 4 / 5: rank path, depth-ordered scatter, round 1's per-tile sort forced
+    for mode in (1, 3, 4):  # 1: what render() runs (rank path at this size), 3 / 4: rank path, depth-ordered scatter forced
         prev = R.set_tile_culling(mode)
         try:
             pro = D._forward_state(rs, *args)
@@ -375,6 +375,19 @@ def test_production_mode_state(oracle):
         else:
             assert pro["num_rendered"] == par["num_rendered"]
         assert pro["rect_instances"] == par["rect_instances"]
+    # tile_culling 5 (the retired per-tile sort) is the library's error, not another path under the old number; the smallest scene
+    cam, sp, bg, deg, mod = scene("cfg1")
+    a = settings_args(cam, bg, deg, mod)
+    rs = GaussianRasterizationSettings(a["H"], a["W"], a["tanfovx"], a["tanfovy"], t(a["bg"]), mod, t(a["viewmatrix"]),
+                                       t(a["projmatrix"]), deg, t(a["campos"]), False, False)
+    args = (t(sp["means3D"]), t(sp["shs"]), None, t(sp["opacities"]), t(sp["scales"]), t(sp["rotations"]), None)
+    prev = R.set_tile_culling(5)
+    try:
+        with pytest.raises(RuntimeError, match="per-tile sort was removed"):
+            D._forward_state(rs, *args)
+    finally:
+        R.set_tile_culling(prev)
+    assert D._forward_state(rs, *args)["num_rendered"] > 0
 
 
 def _same_streams(pro, par, packed=True):
@@ -390,6 +403,21 @@ def _same_streams(pro, par, packed=True):
     ia = np.concatenate([np.arange(a0[q], a0[q] + qc[q]) for q in nz]) if len(nz) else np.zeros(0, np.int64)
     ib = np.concatenate([np.arange(b0[q], b0[q] + qc[q]) for q in nz]) if len(nz) else np.zeros(0, np.int64)
     np.testing.assert_array_equal(qa[ia], qb[ib])
+
+
+def _streams_in_depth_order(st):
+    """Every quadrant stream lists its splats in strictly increasing (depth bits, index) order -- checked from the state's own depths,
+    whatever binning wrote the streams."""
+    qc, q0 = _np(st["qcount"]).astype(np.int64).reshape(-1), _np(st["qstart"]).astype(np.int64).reshape(-1)
+    nz = np.nonzero(qc)[0]
+    if not len(nz):
+        return
+    at = np.concatenate([np.arange(q0[q], q0[q] + qc[q]) for q in nz])
+    idx = _np(st["qpos"]).astype(np.int64)[at]
+    key = (_np(st["depths"]).view(np.uint32).astype(np.int64)[idx] << 32) | idx
+    inside = np.ones(len(at), bool)
+    inside[np.concatenate([[0], np.cumsum(qc[nz])[:-1]])] = False      # the first entry of a stream has no predecessor
+    assert (np.diff(key)[inside[1:]] > 0).all()
 
 
 @pytest.mark.parametrize("name", ["cfg1", "sh2_mod", "culls", "dense_tile", "dense_tile_xl", "depth_ties", "deep_stack", "empty_view"])
@@ -460,8 +488,8 @@ def test_deterministic_backward_is_bit_reproducible(oracle, name):
 
 @pytest.mark.parametrize("seed", range(10))
 def test_rank_path_equals_the_per_tile_sort_on_random_scenes(seed):
-    """The rank path (tile lists ordered through bitmaps of global depth ranks, csrc/gsr_rank.hip) against round 1's per-tile bitonic
-    sort on scenes drawn at random: odd image sizes, splat counts around the wave / workgroup / chunk boundaries, tiny to
+    """The rank path (tile lists ordered through bitmaps of global depth ranks, csrc/gsr_rank.hip), one band and forced bands, against the depth-ordered
+    scatter (csrc/gsr_binning.hip; the per-tile bitonic sort this test is named after was retired) on scenes drawn at random: odd image sizes, splat counts around the wave / workgroup / chunk boundaries, tiny to
     screen-filling splats, everything behind the camera.  Same quadrant streams entry for entry, same image / final_T / radii /
     n_contrib bits, same instance counts."""
     from gaussianavatars_amd import debug as D
@@ -485,31 +513,35 @@ def test_rank_path_equals_the_per_tile_sort_on_random_scenes(seed):
                                        t(a["campos"]), False, False)
     args = (t(sp["means3D"]), t(sp["shs"]), None, t(sp["opacities"]), t(sp["scales"]), t(sp["rotations"]), None)
     out = {}
-    for mode in (3, 6, 5):     # 6: the rank path with a rank per band of tile rows (what frames beyond 262144 splats use)
+    for mode in (3, 6, 4):     # 6: the rank path with a rank per band of tile rows (what frames beyond 262144 splats use)
         prev = R.set_tile_culling(mode)
         try:
             out[mode] = D._forward_state(rs, *args)
         finally:
             R.set_tile_culling(prev)
-    old = out[5]
-    assert old["binning_path"] == 2
+    # the yardstick: the depth-ordered scatter (4), the binning that shares no kernel with the rank path.  (It counts stream entries, not
+    # tile instances: the two rank forms are held to each other there, and to the sum of the tile counters.)
+    old = out[4]
+    assert old["binning_path"] == 1
+    assert out[3]["num_rendered"] == out[6]["num_rendered"]
     for mode in (3, 6):
         new = out[mode]
         assert new["binning_path"] == 0
-        assert new["num_rendered"] == old["num_rendered"] and new["rect_instances"] == old["rect_instances"]
+        assert new["num_rendered"] == int(_np(new["tile_count"]).astype(np.int64).sum()) and new["rect_instances"] == old["rect_instances"]
         for k in ("color", "final_T"):
             assert np.array_equal(_np(new[k]).view(np.uint32), _np(old[k]).view(np.uint32)), (mode, k)
         for k in ("radii", "n_contrib", "n_contrib_q", "tiles_touched"):
             np.testing.assert_array_equal(_np(new[k]), _np(old[k]), err_msg=f"{mode}/{k}")
-        _same_streams(new, old, packed=False)
+        _same_streams(old, new, packed=True)
 
 
 @pytest.mark.parametrize("W,H", [(2560, 2400), (1100, 1600)])
-def test_rank_scatter_forms_on_tile_grids_around_the_staging_limit(W, H):
+def test_rank_scatter_forms_on_tile_grids_around_the_staging_limit(oracle, W, H):
     """k_rscatter / k_rsort_rscatter deal the tile instances evenly to the lanes from staging rows in LDS when those fit beside the tile
     histogram (1100 x 1600: 6900 tiles) and fall back to the lockstep expansion when they do not (2560 x 2400: 24000 tiles = 96 KB of
-    histogram), one band and forced bands: same streams, image bits and counters as round 1's per-tile sort either way.  (Grids beyond the LDS
-    histogram altogether -- per-instance L2 atomics -- are the 3300 x 3300 scene of the oracle tests.)"""
+    histogram), one band and forced bands: the oracle's image bits and counters, and the same depth-ordered streams either way.  (These
+    grids are beyond what the depth-ordered scatter takes, so the yardstick is the CPU oracle.  Grids beyond the LDS histogram altogether --
+    per-instance L2 atomics -- are the 3300 x 3300 scene of the oracle tests.)"""
     from gaussianavatars_amd import debug as D
     from gaussianavatars_amd import rasterizer as R
     from gaussianavatars_amd import synthetic as S
@@ -525,29 +557,34 @@ def test_rank_scatter_forms_on_tile_grids_around_the_staging_limit(W, H):
                                        t(a["campos"]), False, False)
     args = (t(sp["means3D"]), t(sp["shs"]), None, t(sp["opacities"]), t(sp["scales"]), t(sp["rotations"]), None)
     out = {}
-    for mode in (3, 6, 5):
+    for mode in (3, 6):
         prev = R.set_tile_culling(mode)
         try:
             out[mode] = D._forward_state(rs, *args)
         finally:
             R.set_tile_culling(prev)
-    old = out[5]
-    assert old["binning_path"] == 2 and old["num_rendered"] > 20 * P
+    st = oracle.forward(oracle.make_settings(**a), sp["means3D"], sp["shs"], None, sp["opacities"], sp["scales"], sp["rotations"], None)
+    assert out[3]["num_rendered"] == out[6]["num_rendered"] > 20 * P
     for mode in (3, 6):
         new = out[mode]
-        assert new["binning_path"] == 0 and new["num_rendered"] == old["num_rendered"]
+        assert new["binning_path"] == 0 and new["num_rendered"] == int(_np(new["tile_count"]).astype(np.int64).sum())
+        assert new["rect_instances"] == st.num_rendered
         for k in ("color", "final_T"):
-            assert np.array_equal(_np(new[k]).view(np.uint32), _np(old[k]).view(np.uint32)), (mode, k)
-        for k in ("radii", "n_contrib", "n_contrib_q", "tiles_touched"):
-            np.testing.assert_array_equal(_np(new[k]), _np(old[k]), err_msg=f"{mode}/{k}")
-        _same_streams(new, old, packed=False)
+            assert np.array_equal(_np(new[k]).view(np.uint32), getattr(st, k).view(np.uint32)), (mode, k)
+        np.testing.assert_array_equal(_np(new["radii"]), st.radii, err_msg=f"{mode}/radii")
+        np.testing.assert_array_equal(_np(new["tiles_touched"]).astype(np.uint32), st.tiles_touched, err_msg=f"{mode}/tiles_touched")
+        for k in ("n_contrib", "n_contrib_q"):
+            np.testing.assert_array_equal(_np(new[k]), _np(out[3][k]), err_msg=f"{mode}/{k}")
+        _streams_in_depth_order(new)
+    _same_streams(out[6], out[3], packed=False)
 
 
 @pytest.mark.parametrize("W,H,nbands", [(96, 80, 5), (96, 16, 1)])
 def test_rank_bands_with_more_splats_than_one_bitmap_holds(W, H, nbands):
     """300 000 splats crowded into the middle of a small image: past 262144 splats the rank path ranks per band of tile rows, and here
     one band (or, 16 pixels high, the only one) holds more splats than a tile bitmap has bits, so the tile kernel takes several
-    passes over its rank space.  Same streams, image bits and counters as round 1's per-tile sort."""
+    passes over its rank space.  Same streams, image bits and counters as the depth-ordered scatter (the binning that shares no kernel with
+    the rank path; it counts stream entries, so the instance count is held to the sum of the tile counters)."""
     from gaussianavatars_amd import debug as D
     from gaussianavatars_amd import rasterizer as R
     from gaussianavatars_amd import synthetic as S
@@ -563,23 +600,23 @@ def test_rank_bands_with_more_splats_than_one_bitmap_holds(W, H, nbands):
                                        t(a["campos"]), False, False)
     args = (t(sp["means3D"]), t(sp["shs"]), None, t(sp["opacities"]), t(sp["scales"]), t(sp["rotations"]), None)
     out = {}
-    for mode in (3, 5):
+    for mode in (3, 4):
         prev = R.set_tile_culling(mode)
         try:
             out[mode] = D._forward_state(rs, *args)
         finally:
             R.set_tile_culling(prev)
-    new, old = out[3], out[5]
-    assert new["binning_path"] == 0 and old["binning_path"] == 2
+    new, old = out[3], out[4]
+    assert new["binning_path"] == 0 and old["binning_path"] == 1
     assert new["nbands"] == nbands and new["band_rows"] == 1
     if nbands > 1:
         assert int(_np(new["band_total"]).max()) > 262144, "the scene is meant to overflow one band's bitmap"
-    assert new["num_rendered"] == old["num_rendered"] > 262144
+    assert new["num_rendered"] == int(_np(new["tile_count"]).astype(np.int64).sum()) > 262144 and new["rect_instances"] == old["rect_instances"]
     for k in ("color", "final_T"):
         assert np.array_equal(_np(new[k]).view(np.uint32), _np(old[k]).view(np.uint32)), k
     for k in ("radii", "n_contrib", "n_contrib_q"):
         np.testing.assert_array_equal(_np(new[k]), _np(old[k]), err_msg=k)
-    _same_streams(new, old, packed=False)
+    _same_streams(old, new, packed=True)
 
 
 def test_debug_mode_dumps_the_failing_calls_arguments(tmp_path, monkeypatch):

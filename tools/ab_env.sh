@@ -1,5 +1,5 @@
 #!/bin/bash
-# Per-kernel event timings of bench.py with an environment switch off / on:  bash tools/ab_env.sh GSR_RSCATTER_BALANCED "0 1" [bench args]
+# Per-kernel event timings of bench.py with an environment switch off / on:  bash tools/ab_env.sh GSR_RANK_BALANCED "0 1 2" [bench args]
 VAR=$1; VALS=$2; shift 2
 for v in $VALS; do
   env $VAR=$v python bench.py --full --steps 40 --warmup 10 --rounds 1 --min-seconds 0 --no-cpu-baseline --frame-streams 0 "$@" 2>/dev/null | python -c "
