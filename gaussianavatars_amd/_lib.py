@@ -592,7 +592,7 @@ gev_profile_read = partial(profile_read, ("gev",))
 FRAME_LIBS = {}
 
 GFS_LIB_PATH = _lib_path("gfs")
-GFS_ABI_VERSION = 1
+GFS_ABI_VERSION = 2
 GFS_E_RANGE = -3               # include/gfs.h: a host index outside the store
 GFS_TABLE_ENTRIES = 256        # include/gfs.h: floats of the byte-to-float table
 GFS_MAX_BATCH = 65535          # include/gfs.h: frames per gfs_fetch_batch / gfs_compose launch
@@ -603,6 +603,9 @@ GFS_SYMBOLS = {
     "gfs_last_error": (C.c_char_p, []),
     "gfs_frame_stride": (C.c_int64, [C.c_int32, C.c_int32]),
     "gfs_compose": (C.c_int, [C.c_int32, C.c_int32, _P, C.POINTER(C.c_double), _P, C.c_int64, C.c_int64, C.c_int32, _P]),
+    "gfs_resample_tmp_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "gfs_resample": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P,
+                               C.c_int64, C.c_int64, C.c_int32, _P]),
     "gfs_fetch": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int64, C.c_int64, _P, _P, _P]),
     "gfs_fetch_indexed": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P, _P, _P]),
     "gfs_fetch_batch": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, _P, _P, _P]),

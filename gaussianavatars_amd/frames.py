@@ -12,9 +12,12 @@ The reference composes, quantises to bytes, divides by 255 and clamps for every 
 (scene/__init__.py:38-63), ships the 3xHxW fp32 result across a process boundary and uploads it from pageable memory (train.py:128).  Here a
 worker's `__getitem__` copies the camera and attaches two small Python objects; the bytes never leave the device.
 
-A frame is resident when its file decodes to the camera's own `image_width` x `image_height` (PIL's resampling is not restated), its
-background is three numbers, its three camera tensors are fp32 and the store's byte budget still has room.  Every other frame keeps the
-reference's path, frame by frame.
+A frame is resident when its background is three numbers, its three camera tensors are fp32, the store's byte budget still has room and its
+file decodes to the camera's own `image_width` x `image_height` -- or, under `from_cameras(..., resample=True)`, to any other size: the
+composited bytes then go through PILtoTorch's `pil_image.resize(resolution)` (utils/general_utils.py:22) on the way in, restated exactly:
+Pillow's bicubic resize of an 8-bit image is two integer passes over fixed-point coefficients (resample_tables, resample_composed,
+gfs_resample), and the frame is stored at the camera's size like any other.  Without `resample` PIL's resampling is not restated and such a
+frame is not resident.  Every frame that is not resident keeps the reference's path, frame by frame.
 
 Device stores run on the kernels.  Host stores, and GAA_FRAME_STORE=0, evaluate the composed torch expressions below, which give the same
 bits and are what the CPU tests hold to the pins.  A missing library is an error, never a reason to take the composed path.
@@ -22,7 +25,9 @@ bits and are what the CPU tests hold to the pins.  A missing library is an error
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import itertools
+import math
 import os
 from copy import deepcopy
 
@@ -38,6 +43,12 @@ _CHUNK = 32               # frames decoded, uploaded and composited together
 def fused_default() -> bool:
     """GAA_FRAME_STORE=0: no adoption by patch_reference(), and every call takes the composed-torch path (A/B runs)."""
     return os.environ.get("GAA_FRAME_STORE", "1") != "0"
+
+
+def resize_default() -> bool:
+    """GAA_FRAME_STORE_RESIZE=1: the stores patch.adopt_frame_store builds also hold the frames whose camera asks for another size than its
+    file's (`from_cameras(..., resample=True)`).  Off unless set; read where GAA_FRAME_STORE is, when a store is built."""
+    return os.environ.get("GAA_FRAME_STORE_RESIZE", "0") == "1"
 
 
 def _check(rc, what):
@@ -72,6 +83,99 @@ def fetch_composed(rgb: torch.Tensor, table: torch.Tensor | None = None) -> torc
     division is a look-up in `table` (byte_table(), divided on the host), for the reason compose_composed gives."""
     f = rgb / 255.0 if table is None else table[rgb.to(torch.int64)]
     return f.permute(2, 0, 1).clamp(0.0, 1.0)
+
+
+# ---- Pillow's bicubic resize of 8-bit images, restated (libImaging/Resample.c) -----------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def resample_tables(in_size: int, out_size: int):
+    """One axis of `PIL.Image.resize` with its defaults (bicubic): -> (coefficients int32 (out, ksize), bounds int32 (out, 2)) as host tensors,
+    bounds[i] = (first source index, taps) and coefficients[i, taps:] = 0; None when the size does not change (Pillow skips that axis).
+    precompute_coeffs and normalize_coeffs_8bpc in IEEE doubles, operation by operation in Resample.c's order, on the host: the weights are
+    summed tap by tap (no pairwise sum), divided by the sum, scaled by 2^22 and rounded half away from zero by a truncation.  Computed once per
+    (in, out) and shared: the tensors are not to be written."""
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size <= 0 or out_size <= 0:
+        raise ValueError(f"resample_tables({in_size}, {out_size}): sizes must be positive")
+    if in_size == out_size:
+        return None
+    scale = np.float64(in_size) / np.float64(out_size)
+    fs = max(scale, np.float64(1.0))
+    support = np.float64(2.0) * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = np.float64(1.0) / fs
+    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    first = np.maximum((center - support + 0.5).astype(np.int64), 0)             # (a C cast: toward zero)
+    taps = np.minimum((center + support + 0.5).astype(np.int64), in_size) - first
+    tap = np.arange(ksize, dtype=np.int64)[None, :]
+    t = np.abs(((tap + first[:, None]).astype(np.float64) - center[:, None] + 0.5) * ss)
+    a = np.float64(-0.5)
+    near = ((a + 2.0) * t - (a + 3.0)) * t * t + 1
+    far = (((t - 5) * t + 8) * t - 4) * a
+    w = np.where(tap < taps[:, None], np.where(t < 1.0, near, np.where(t < 2.0, far, 0.0)), 0.0)
+    total = np.zeros(out_size, np.float64)
+    for x in range(ksize):                                                        # in index order, as the C loop adds them
+        total = total + w[:, x]
+    w = np.where(total[:, None] != 0.0, w / np.where(total != 0.0, total, 1.0)[:, None], w)
+    fixed = np.where(w < 0, -0.5 + w * float(1 << 22), 0.5 + w * float(1 << 22)).astype(np.int64).astype(np.int32)
+    return torch.from_numpy(np.ascontiguousarray(fixed)), torch.from_numpy(np.ascontiguousarray(np.stack([first, taps], axis=1).astype(np.int32)))
+
+
+def _resample_axis(x: torch.Tensor, dim: int, tables) -> torch.Tensor:
+    """ImagingResampleHorizontal_8bpc / Vertical_8bpc along `dim` of a uint8 tensor: int32 products and sum, 2^21 added, an arithmetic shift by
+    22, the clamp to a byte.  One gather per tap, so nothing larger than the output is ever held."""
+    coef, bounds = (t.to(x.device) for t in tables)
+    first, last = bounds[:, 0].to(torch.int64), (bounds[:, 1] - 1).to(torch.int64)
+    shape = [1] * x.dim()
+    shape[dim] = coef.shape[0]
+    x = x.to(torch.int32)
+    acc = None
+    for t in range(coef.shape[1]):
+        term = x.index_select(dim, first + torch.clamp(last, max=t)) * coef[:, t].view(shape)   # (behind its taps a coefficient is zero)
+        acc = term + (1 << 21) if acc is None else acc + term
+    return (acc >> 22).clamp(0, 255).to(torch.uint8)
+
+
+def resample_composed(rgb, size):
+    """`Image.fromarray(rgb, "RGB").resize(size)` on (..., H, W, 3) uint8, torch (any device) or numpy, `size` = (width, height) as PIL takes it:
+    the horizontal axis first, bytes in between, the vertical axis second, an unchanged axis skipped.  -> (..., height, width, 3) uint8 of the
+    same kind."""
+    if isinstance(rgb, np.ndarray):
+        return resample_composed(torch.from_numpy(np.ascontiguousarray(rgb)), size).numpy()
+    if rgb.dtype is not torch.uint8 or rgb.dim() < 3 or rgb.shape[-1] != 3:
+        raise ValueError(f"resample_composed takes (..., H, W, 3) uint8, got {tuple(rgb.shape)} {rgb.dtype}")
+    W, H = int(size[0]), int(size[1])
+    for dim, want in ((rgb.dim() - 2, W), (rgb.dim() - 3, H)):
+        tables = resample_tables(rgb.shape[dim], want)
+        if tables is not None:
+            rgb = _resample_axis(rgb, dim, tables)
+    return rgb.contiguous()
+
+
+class _Staging:
+    """What the resize needs while a store is built and not afterwards: a group of _CHUNK frames per source size, the image between the two
+    passes, and the tables on the device."""
+
+    def __init__(self, device):
+        self.device, self.groups, self.tmp, self.tables = device, {}, None, {}
+
+    def group(self, hw):
+        if hw not in self.groups:
+            self.groups[hw] = _Group(hw[0], hw[1], _CHUNK, self.device)
+        return self.groups[hw]
+
+    def axis(self, in_size, out_size):
+        """(coefficients pointer, bounds pointer, ksize) of one axis on the device; (None, None, 0) when the size does not change."""
+        if in_size == out_size:
+            return None, None, 0
+        if (in_size, out_size) not in self.tables:
+            self.tables[(in_size, out_size)] = tuple(t.to(self.device) for t in resample_tables(in_size, out_size))
+        coef, bounds = self.tables[(in_size, out_size)]
+        return coef.data_ptr(), bounds.data_ptr(), coef.shape[1]
+
+    def between(self, nbytes):
+        if self.tmp is None or self.tmp.numel() < nbytes:
+            self.tmp = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self.tmp
 
 
 # ---- the process-local registry ------------------------------------------------------------------------------------------------------------
@@ -222,25 +326,29 @@ class FrameStore:
 
     # ---- building ---------------------------------------------------------------------------------------------------------------------------
     @classmethod
-    def from_cameras(cls, cameras, device, budget_bytes=None) -> "FrameStore":
+    def from_cameras(cls, cameras, device, budget_bytes=None, resample=False) -> "FrameStore":
         """Decodes each camera's `image` or `image_path` with PIL `convert("RGBA")` on a pool of at most MAX_DECODE_THREADS threads, uploads
         the raw RGBA bytes and composites them over `camera.bg` on the device.  `budget_bytes`: what the frames may take (default_budget()
-        when None); the cameras are admitted in order until it is spent, the rest stay non-resident."""
+        when None); the cameras are admitted in order until it is spent, the rest stay non-resident.  `resample`: a camera whose file is
+        not `image_width` x `image_height` is admitted too, and its composited bytes are resized to that size as PIL would (gfs_resample);
+        the frame is stored, and counted against the budget, at the camera's size.  The source-size staging lives only during this call."""
         self = cls(device)
         cameras = list(cameras)
         budget = default_budget(self.device) if budget_bytes is None else int(budget_bytes)
-        plan, rows, capacity, used = [], [], {}, 0
+        plan, rows, capacity, used = [], [], {}, 0   # plan: per camera (its group (H, W), slot, background, the file's (H, W)) or None
         for cam in cameras:
             size, bg, row = _image_size(cam), _background(cam), _camera_row(cam)
-            ok = (size is not None and bg is not None and row is not None
-                  and size == (int(cam.image_width), int(cam.image_height)) and size[0] > 0 and size[1] > 0)
+            ok = size is not None and bg is not None and row is not None and size[0] > 0 and size[1] > 0
             if ok:
-                need = frame_stride(size[1], size[0])
+                want = (int(cam.image_width), int(cam.image_height))
+                ok = size == want or (resample and want[0] > 0 and want[1] > 0)
+            if ok:
+                need = frame_stride(want[1], want[0])
                 ok = budget is None or used + need <= budget
             if ok:
                 used += need
-                hw = (size[1], size[0])
-                plan.append((hw, capacity.get(hw, 0), bg))
+                hw = (want[1], want[0])
+                plan.append((hw, capacity.get(hw, 0), bg, (size[1], size[0])))
                 capacity[hw] = capacity.get(hw, 0) + 1
             else:
                 plan.append(None)
@@ -253,22 +361,58 @@ class FrameStore:
         if todo:
             from concurrent.futures import ThreadPoolExecutor
 
+            staging = _Staging(self.device)
             with ThreadPoolExecutor(max_workers=min(MAX_DECODE_THREADS, len(todo))) as pool:
                 for c0 in range(0, len(todo), _CHUNK):
                     chunk = todo[c0:c0 + _CHUNK]
                     images = list(pool.map(_decode, [cameras[i] for i in chunk]))
-                    # runs of consecutive frames of one group and one background go up together: their slots are consecutive too
+                    # runs of consecutive frames of one group, one file size and one background go up together: their slots are consecutive too
                     a = 0
                     while a < len(chunk):
-                        hw, slot, bg = plan[chunk[a]]
+                        hw, slot, bg, file_hw = plan[chunk[a]]
                         b = a + 1
-                        while b < len(chunk) and plan[chunk[b]][0] == hw and np.array_equal(plan[chunk[b]][2], bg):
+                        while b < len(chunk) and plan[chunk[b]][0] == hw and plan[chunk[b]][3] == file_hw and np.array_equal(plan[chunk[b]][2], bg):
                             b += 1
-                        if any(im.shape != (hw[0], hw[1], 4) for im in images[a:b]):
+                        if any(im.shape != (file_hw[0], file_hw[1], 4) for im in images[a:b]):
                             raise RuntimeError(f"an image of {cameras[chunk[a]].image_name!r} .. changed size between the header and the decode")
-                        self.ingest(hw, slot, torch.from_numpy(np.stack(images[a:b])), bg)
+                        rgba = torch.from_numpy(np.stack(images[a:b]))
+                        if file_hw == hw:
+                            self.ingest(hw, slot, rgba, bg)
+                        else:
+                            self.ingest_resized(hw, slot, rgba, bg, staging)
                         a = b
         return self
+
+    def ingest_resized(self, hw, first: int, rgba: torch.Tensor, bg, staging: "_Staging | None" = None) -> None:
+        """Composites `rgba` ((n, Hs, Ws, 4) uint8 of any size, host or device) over `bg` at its own size and resizes the bytes to the group `hw`
+        as `PIL.Image.resize` would, into frames first .. first + n - 1: the upload, gfs_compose into a staging group of the source size,
+        gfs_resample from there into the slots, _CHUNK frames at a time.  `staging` is reused across calls by from_cameras and dropped with it."""
+        g = self.groups[tuple(hw)]
+        n, HW3 = rgba.shape[0], g.H * g.W * 3
+        if rgba.dtype is not torch.uint8 or rgba.dim() != 4 or rgba.shape[3] != 4 or min(rgba.shape) < 1 or first < 0 or first + n > g.capacity:
+            raise ValueError(f"ingest of {tuple(rgba.shape)} at {first} into a group of {g.capacity} frames of {(g.H, g.W)}")
+        Hs, Ws = int(rgba.shape[1]), int(rgba.shape[2])
+        if (Hs, Ws) == (g.H, g.W):
+            return self.ingest(hw, first, rgba, bg)
+        bg = np.asarray(bg, np.float64).reshape(3)
+        if self.device.type == "cuda" and fused_default():
+            staging = _Staging(self.device) if staging is None else staging
+            src, lib, stream = staging.group((Hs, Ws)), _lib.gfs(), _lib.raw_stream(self.device)
+            kx, bx, ksx = staging.axis(Ws, g.W)
+            ky, by, ksy = staging.axis(Hs, g.H)
+            tmp = staging.between(lib.gfs_resample_tmp_bytes(Hs, g.W, src.capacity)).data_ptr() if ksx and ksy else None
+            with _lib.on_device(self.device):
+                for a in range(0, n, src.capacity):
+                    k = min(src.capacity, n - a)
+                    part = rgba[a:a + k].to(self.device).contiguous()
+                    _check(lib.gfs_compose(Hs, Ws, part.data_ptr(), (C.c_double * 3)(*bg), src.frames.data_ptr(), src.capacity, 0, k, stream), "gfs_compose")
+                    _check(lib.gfs_resample(Hs, Ws, src.frames.data_ptr(), src.capacity, 0, g.H, g.W, kx, bx, ksx, ky, by, ksy, tmp, g.frames.data_ptr(),
+                                            g.capacity, first + a, k, stream), "gfs_resample")
+        else:
+            for a in range(n):   # (a frame at a time: the fp64 composite of a source-size image is eight times its bytes)
+                part = compose_composed(rgba[a].to(self.device), bg)
+                g.frames.view(g.capacity, g.stride)[first + a, :HW3] = resample_composed(part, (g.W, g.H)).reshape(HW3)
+        g.count = max(g.count, first + n)
 
     def ingest(self, hw, first: int, rgba: torch.Tensor, bg) -> None:
         """Composites `rgba` ((n, H, W, 4) uint8, host or device) over `bg` into frames first .. first + n - 1 of the group `hw`."""

@@ -396,7 +396,7 @@ def _make_resident_getter(orig, name, device):
         hit = cache.get((name, scale))
         if hit is None or hit[0] is not dataset.cameras:   # (built on the first call, in the process that makes it: before train.py:55 forks its workers)
             dev = device if device is not None else torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-            hit = cache[(name, scale)] = (dataset.cameras, FR.FrameStore.from_cameras(dataset.cameras, dev))
+            hit = cache[(name, scale)] = (dataset.cameras, FR.FrameStore.from_cameras(dataset.cameras, dev, resample=FR.resize_default()))
         return FR.ResidentCameraDataset(dataset.cameras, hit[1], fallback=dataset)
 
     getter.__name__ = name
@@ -409,7 +409,8 @@ def adopt_frame_store(scene_cls=None, device=None) -> list:
     `scene_cls`, any class whose getters return a dataset with a `cameras` list) so that it returns a frames.ResidentCameraDataset over a
     frames.FrameStore on `device` (default: the current GPU; the host without one).  The store is built at the first call -- train.py:55, in the
     main process, before the DataLoader forks its workers -- and kept on the Scene object, one per (getter, scale); train.py and its DataLoader
-    line stay unedited.  Frames the store does not hold (budget, a size other than the file's) run the reference's own `__getitem__`.
+    line stay unedited.  Frames the store does not hold (budget, a size other than the file's) run the reference's own `__getitem__`; under
+    GAA_FRAME_STORE_RESIZE=1 (read when the store is built) frames of another size than their file's are held too, resized as PIL resizes them.
     `getValCameras` / `getTestCameras` are wrapped only under GAA_FRAME_STORE_EVAL=1.  GAA_FRAME_STORE=0 (read at every call of the getter, and
     by patch_reference()) gives the reference's dataset.  Without an importable `scene.Scene` nothing is rebound.  Idempotent; undone by
     unpatch_classes.  Returns the names rebound."""

@@ -4,6 +4,9 @@
  *
  *   gfs_compose        scene/__init__.py:48-51 (CameraDataset.__getitem__): the decoded RGBA bytes composited over
  *                      the camera's background in fp64 and quantised back to bytes, once per frame, at ingest.
+ *   gfs_resample       scene/__init__.py:54 (PILtoTorch's `pil_image.resize(resolution)`) for a camera that asks for another size than
+ *                      its file's (--resolution 2/4/8, -r WIDTH, the rescale of images wider than 1600 px): Pillow's bicubic resize
+ *                      of the composited bytes, byte for byte, once per frame, at ingest.
  *   gfs_fetch*         scene/__init__.py:54-62 (PILtoTorch at the file's own size, [:3], clamp): one stored frame as
  *                      the planar fp32 (3,H,W) `original_image` train.py:128 uploads, in one launch.
  *
@@ -25,7 +28,7 @@
 extern "C" {
 #endif
 
-#define GFS_ABI_VERSION 1
+#define GFS_ABI_VERSION 2
 #define GFS_OK 0
 #define GFS_E_ARG (-1)
 #define GFS_E_HIP (-2)
@@ -47,6 +50,22 @@ int64_t gfs_frame_stride(int32_t H, int32_t W);
  * One launch; a lane takes four pixels (one 16-byte load where the source allows, three dword stores). */
 int gfs_compose(int32_t H, int32_t W, const uint8_t* rgba, const double* bg, uint8_t* store, int64_t capacity, int64_t first, int32_t count,
                 void* stream);
+
+/* `PIL.Image.resize((Wout, Hout))` with its defaults (bicubic, no reducing_gap) of `count` stored "RGB" frames: frames src_first .. of `src`
+ * (a store of src_capacity frames of Hin x Win) -> frames first .. first + count - 1 of `store` (capacity frames of Hout x Wout).  The two
+ * stores must not overlap.  Pillow's passes, in its order: the horizontal axis, bytes, the vertical axis; an axis whose size does not
+ * change is skipped.  Per axis and output index i, with the HOST-computed tables of that axis (DEVICE pointers; frames.resample_tables):
+ *   k: int32 (out, ks), the weights of Resample.c's precompute_coeffs in fp64, normalised, times 2^22, rounded half away from zero
+ *   b: int32 (out, 2), (first source index, taps); a kernel holds them to the axis and to ks, and they must not decrease with i
+ *   byte = clamp((2^21 + sum_{t < taps} source_byte[first + t] * k[i][t]) >> 22, 0, 255)       (int32 sum, arithmetic shift)
+ * The coefficients are not formed here: this translation unit multiplies bytes by integers and nothing else, so no contraction or
+ * reassociation can move a last bit.  kx / bx are null exactly when Win == Wout, ky / by exactly when Hin == Hout; at least one axis changes.
+ * tmp: gfs_resample_tmp_bytes(Hin, Wout, count) bytes, 16-byte aligned, needed (and touched) only when both axes change.
+ * Every byte of a destination frame's stride behind its last pixel is written as zero.  One launch per pass, each over all `count` frames. */
+int64_t gfs_resample_tmp_bytes(int32_t Hin, int32_t Wout, int32_t count);   /* 0 for a bad shape or count */
+int gfs_resample(int32_t Hin, int32_t Win, const uint8_t* src, int64_t src_capacity, int64_t src_first, int32_t Hout, int32_t Wout,
+                 const int32_t* kx, const int32_t* bx, int32_t ksx, const int32_t* ky, const int32_t* by, int32_t ksy, uint8_t* tmp, uint8_t* store,
+                 int64_t capacity, int64_t first, int32_t count, void* stream);
 
 /* frame `index` (HOST value; GFS_E_RANGE outside [0, count)) of `store` -> out: float (3,H,W), out[c][y][x] = table[byte].
  * table: GFS_TABLE_ENTRIES floats, `torch.arange(256, dtype=uint8) / 255.0` computed by the caller: the kernel stages it in LDS and never

@@ -13,6 +13,9 @@ frames after `warmup` calls, timed by the host clock around the window, which en
 when the copy is staged, a launch when it is enqueued: neither is the frame being there).  The figure is the median over the rounds, the spread
 its minimum and maximum.  Both sides deliver the same bits (checked before anything is timed).  One JSON line.
 
+    e  resize     a second JSON line (resize_row below): a store under `resample=True` over files of 3208 x 2200 for cameras of 802 x 550,
+                  per frame, against the reference's worker `__getitem__` plus upload per iteration; the two resize kernels alone
+
 What this does not measure: the DataLoader workers' decode and composite per frame and the worker-queue hop of the 5.3 MB tensor, which the
 resident path also removes, and the effect on train.py's `iter_time` end to end.
 
@@ -73,6 +76,8 @@ def main():
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--height", type=int, default=550)
     ap.add_argument("--width", type=int, default=802)
+    ap.add_argument("--resize-frames", type=int, default=4, help="frames of the resize line (0: leave it out)")
+    ap.add_argument("--resize-from", type=int, nargs=2, default=(2200, 3208), metavar=("H", "W"), help="size of the files of the resize line")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("frames_timing.py measures on the GPU; there is none here")
@@ -145,6 +150,93 @@ def main():
     row["c_fetch_GBps_at_median"] = moved / (statistics.median(c) * 1e-3) / 1e9
     row["c_note"] = "back-to-back launches by device events: the rate includes the launch gaps of a 6.6 MB pass"
     print(json.dumps(row), flush=True)
+    store.release()
+    if args.resize_frames > 0:
+        print(json.dumps(resize_row(args, dev)), flush=True)
+
+
+def worker_getitem(camera):
+    """What a DataLoader worker of the reference does for a camera whose size is not its file's (scene/__init__.py:41-63, PILtoTorch): decode,
+    the fp64 composite on the host, bytes, `resize`, / 255, clamp -> the pageable fp32 tensor train.py:128 uploads."""
+    from PIL import Image
+
+    n = np.array(Image.open(camera.image_path).convert("RGBA")) / 255.0
+    arr = n[:, :, :3] * n[:, :, 3:4] + camera.bg * (1 - n[:, :, 3:4])
+    image = Image.fromarray(np.array(arr * 255.0, dtype=np.byte).view(np.uint8), "RGB").resize((camera.image_width, camera.image_height))
+    return (torch.from_numpy(np.array(image)) / 255.0).permute(2, 0, 1).clamp(0.0, 1.0)
+
+
+def resize_row(args, dev):
+    """e  resize: files of --resize-from (3208 x 2200) for cameras of a quarter of that (802 x 550).  The build of a store over them under
+    `resample=True` (decode on the thread pool, upload, gfs_compose at the file's size, gfs_resample), per frame and once; against what the
+    path it replaces costs per ITERATION: worker_getitem in this process plus the `.cuda()` of its result (in training the first half runs in
+    a DataLoader worker, beside the step rather than inside it, and crosses a queue, which is not timed here).  The two kernels alone by
+    device events, with the bytes they have to move."""
+    from PIL import Image
+
+    Hs, Ws = args.resize_from
+    H, W, N = Hs // 4, Ws // 4, args.resize_frames
+    g = np.random.default_rng(12)
+    row = {"resize": {"file": [Hs, Ws], "image": [H, W]}, "frames": N, "pillow": Image.__version__}
+    with tempfile.TemporaryDirectory() as tmp:
+        cams = []
+        for i in range(N):
+            c = S.orbit_camera(W, H, yaw_deg=10.0 * i)
+            rgba = g.integers(0, 256, (Hs, Ws, 4), dtype=np.uint8)
+            rgba[..., 3] = np.where(g.random((Hs, Ws)) < 0.7, 255, rgba[..., 3])
+            path = os.path.join(tmp, f"{i:05d}.png")
+            Image.fromarray(rgba, "RGBA").save(path, compress_level=1)
+            cams.append(argparse.Namespace(image=None, image_path=path, bg=np.array([1.0, 1.0, 1.0]), image_width=W, image_height=H, image_name=str(i),
+                                           world_view_transform=torch.as_tensor(c.world_view_transform.T.copy()).transpose(0, 1),
+                                           full_proj_transform=torch.as_tensor(c.full_proj_transform.T.copy()).transpose(0, 1),
+                                           camera_center=torch.as_tensor(c.camera_center)))
+        FR.FrameStore.from_cameras(cams[:1], dev, resample=True).release()   # (maps the library, loads the code object, builds the tables)
+        build = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            store = FR.FrameStore.from_cameras(cams, dev, resample=True)
+            torch.cuda.synchronize()
+            build.append(1e3 * (time.perf_counter() - t0) / N)
+            if len(build) < 3:
+                store.release()
+        row["e_build_per_frame"] = _spread(build)
+        row["e_decode_threads"] = min(FR.MAX_DECODE_THREADS, N)
+        replaced, same = [], True
+        for _ in range(3):
+            for i, cam in enumerate(cams):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                gt = worker_getitem(cam).cuda()
+                torch.cuda.synchronize()
+                replaced.append(1e3 * (time.perf_counter() - t0))
+                same = same and torch.equal(gt, store.image(i))
+        row["e_replaced_per_iteration"] = _spread(replaced)
+        row["e_same_bits"] = bool(same)
+    assert all(store.resident(i) for i in range(N))
+    # the two passes alone, over the N composited source-size frames
+    staging = FR._Staging(dev)
+    src, out = staging.group((Hs, Ws)), store.groups[(H, W)]
+    src.frames.copy_(torch.from_numpy(g.integers(0, 256, src.frames.numel(), dtype=np.uint8)))
+    kx, bx, ksx = staging.axis(Ws, W)
+    ky, by, ksy = staging.axis(Hs, H)
+    lib, stream = _lib.gfs(), _lib.raw_stream(dev)
+    tmp_dev = staging.between(lib.gfs_resample_tmp_bytes(Hs, W, N))
+    _lib.gfs_profile_enable(True)
+    for _ in range(3 + args.rounds):
+        rc = lib.gfs_resample(Hs, Ws, src.frames.data_ptr(), src.capacity, 0, H, W, kx, bx, ksx, ky, by, ksy, tmp_dev.data_ptr(), out.frames.data_ptr(),
+                              out.capacity, 0, N, stream)
+        assert rc == 0, _lib.gfs_error()
+    prof = _lib.gfs_profile_read()
+    _lib.gfs_profile_enable(False)
+    moved = {"gfs::k_resample_h": N * (FR.frame_stride(Hs, Ws) + FR.frame_stride(Hs, W)), "gfs::k_resample_v": N * (FR.frame_stride(Hs, W) + FR.frame_stride(H, W))}
+    for name, nbytes in moved.items():
+        ms, launches = prof[name]
+        row["e_" + name.split("::")[1]] = {"mean_ms_per_launch": ms / launches, "launches": launches, "frames_per_launch": N, "bytes": nbytes,
+                                           "GBps": nbytes / (ms / launches * 1e-3) / 1e9}
+    row["e_note"] = "kernel times: an event pair around each launch (the library's profile shim), code objects loaded by the builds before"
+    store.release()
+    return row
 
 
 if __name__ == "__main__":
