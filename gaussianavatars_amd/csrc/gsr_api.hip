@@ -1,6 +1,7 @@
 // gsr_api.hip -- the C ABI of include/gsr.h: argument checks, state-buffer layouts, the host
-// mailbox for the instance count, and the launch sequence.  No torch types; callers hand in raw
-// device pointers and a hipStream_t.
+// mailbox for the instance count, typed views of the three state buffers, and the launch chains of a frame: k_preprocess, one of
+// the two binning chains (depth-ordered scatter k_dbucket .. k_qscatter, or rank path k_rcount .. k_tile_rank), k_render; and
+// k_render_bwd(_rp), k_preprocess_bwd.  Host code only.  No torch types; callers hand in raw device pointers and a hipStream_t.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -16,7 +17,9 @@
 #include <vector>
 
 #include "gsr_device.h"
+#include "gsr_views.h"
 
+using namespace gsr_host;
 
 namespace {
 
@@ -74,6 +77,34 @@ struct Mailbox {
 Mailbox g_mail;
 std::atomic<long long> g_wait_ns{0}, g_waits{0};
 thread_local long long g_last_seq = 0;   // the sequence number of this thread's newest forward (gsr_last_forward_seq)
+
+// The one wait for a post: spins on `word` until it holds sequence number `seq` (*v: the posted word), yields after 2000 spins, and every
+// 4096 spins asks whether the stream drained (or faulted) without the post or 120 s have passed.  Accounts the wait for gsr_wait_stats.
+static int await_post(const unsigned long long* word, unsigned long long seq, hipStream_t stream, unsigned long long* v)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned spins = 0;
+    for (;;) {
+        *v = __atomic_load_n(word, __ATOMIC_ACQUIRE);
+        if (*v != 0 && (*v >> 40) == seq) break;
+        if (++spins > 2000) {
+            std::this_thread::yield();
+            if ((spins & 0xFFF) == 0) {
+                if (hipStreamQuery(stream) != hipErrorNotReady) {   // stream drained (or faulted) without the post
+                    *v = __atomic_load_n(word, __ATOMIC_ACQUIRE);
+                    if (*v != 0 && (*v >> 40) == seq) break;
+                    hipError_t e = hipStreamSynchronize(stream);
+                    return fail(GSR_E_HIP, "stream finished without posting the instance count: %s", hipGetErrorString(e));
+                }
+                if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(120))
+                    return fail(GSR_E_TIMEOUT, "timed out waiting for the instance count");
+            }
+        }
+    }
+    g_wait_ns.fetch_add((long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count());
+    g_waits.fetch_add(1);
+    return GSR_OK;
+}
 
 // ---- optional per-kernel event timing -------------------------------------------------------
 struct Profiler {
@@ -200,6 +231,24 @@ int rank_ilv_for(int device, int W, int H)
     auto it = g_ilv_hint.find(std::make_tuple(device, W, H));
     return it != g_ilv_hint.end() && it->second ? GSR_RANK_ILV_AUTO : 0;
 }
+// The `ilv` argument of the rank path's chunked passes for this frame: contiguous chunks of splats per workgroup (-1), or -- when the previous frame of this
+// (device, size) reported its tile instances unevenly spread along the splat order -- small groups dealt round-robin (log2 of the group size; gsr_device.h:
+// rank_chunk / rank_splat; this frame's own report rides in the posted count), or balanced chunks (-2)
+int rank_chunking(int device, int W, int H, int32_t P, int nbands)
+{
+    const int ilv = rank_ilv_for(device, W, H);   // 0: contiguous, else a group size (rounded down to a power of two)
+    int rank_ilv = -1;
+    for (int v = ilv; v > 0; v >>= 1) ++rank_ilv;   // log2, -1 for contiguous
+    // ... and on frames of one band the answer to an uneven spread is not the interleave but contiguous chunks of equal WEIGHT, cut by k_rcount from
+    // k_preprocess's group sums (gsr_device.h: rank_map; round 6): the template-like head's scatter 44 -> 31 us where the interleave had brought it from
+    // 88 to 44, and k_rcount keeps its compact set of tiles.  (It costs k_rcount 3.5 us of prologue, so an even frame keeps its equal-count chunks.)
+    // GSR_RANK_BALANCED=0: the interleave; =2: balanced chunks on every frame (A/B runs)
+    static const int balanced = [] { const char* e = getenv("GSR_RANK_BALANCED"); return e ? atoi(e) : 1; }();
+    static const bool forced_ilv = getenv("GSR_RANK_ILV") != nullptr;
+    const bool can = (long long)P <= (long long)GSR_RANK_MAX_SPLATS && nbands <= 1 && !forced_ilv;
+    if (can && ((balanced == 1 && ilv > 0) || balanced == 2)) rank_ilv = -2;
+    return rank_ilv;
+}
 void slot_holds_frame(int slot_index, int device, int W, int H)
 {
     std::lock_guard<std::mutex> lock(g_ilv_mutex);
@@ -230,30 +279,8 @@ int gsr_count_slot_wait(int32_t slot, int64_t want_seq, void* stream_, int64_t* 
 {
     if (slot < 0 || slot >= GSR_COUNT_SLOTS || !count || want_seq <= 0) return fail(GSR_E_ARG, "gsr_count_slot_wait: bad arguments");
     if (int rc = g_mail.init()) return rc;
-    hipStream_t stream = (hipStream_t)stream_;
-    const unsigned long long* w = g_mail.host + Mailbox::kSlots + slot;
-    const auto t0 = std::chrono::steady_clock::now();
     unsigned long long v;
-    unsigned spins = 0;
-    for (;;) {
-        v = __atomic_load_n(w, __ATOMIC_ACQUIRE);
-        if (v != 0 && (long long)(v >> 40) == want_seq) break;
-        if (++spins > 2000) {
-            std::this_thread::yield();
-            if ((spins & 0xFFF) == 0) {
-                if (hipStreamQuery(stream) != hipErrorNotReady) {   // stream drained (or faulted) without the post
-                    v = __atomic_load_n(w, __ATOMIC_ACQUIRE);
-                    if (v != 0 && (long long)(v >> 40) == want_seq) break;
-                    hipError_t e = hipStreamSynchronize(stream);
-                    return fail(GSR_E_HIP, "stream finished without posting the instance count: %s", hipGetErrorString(e));
-                }
-                if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(120))
-                    return fail(GSR_E_TIMEOUT, "timed out waiting for the instance count");
-            }
-        }
-    }
-    g_wait_ns.fetch_add((long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count());
-    g_waits.fetch_add(1);
+    if (int rc = await_post(g_mail.host + Mailbox::kSlots + slot, (unsigned long long)want_seq, (hipStream_t)stream_, &v)) return rc;
     *count = (int64_t)(v & kCountMask);
     note_posted(slot, v);
     return GSR_OK;
@@ -326,15 +353,14 @@ int gsr_binning_layout(int64_t capacity, int32_t width, int32_t height, int32_t 
 {
     if (!o || capacity < 0 || width <= 0 || height <= 0 || P < 0) return fail(GSR_E_ARG, "gsr_binning_layout: bad arguments");
     if (int rc = check_tile_culling(tile_culling)) return rc;
-    const size_t tiles = (size_t)((width + GSR_BLOCK_X - 1) / GSR_BLOCK_X) * (size_t)((height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y);
-    const size_t cap = (size_t)capacity, A = 256, n = (size_t)P;
+    const TileGrid tg = tile_grid(width, height);
+    const size_t tiles = tg.tiles, cap = (size_t)capacity, A = 256, n = (size_t)P;
     size_t chunks, nb;
     const int path = binning_path(P, tiles, tile_culling, &chunks, &nb);
     const bool prod = path == 1, rankp = path == 0;
-    const bool lists = tile_culling == 0 || tile_culling == 2;     // the reference-format key / point lists are materialised
+    const bool lists = reference_lists(tile_culling);
     const size_t Q = 4 * tiles, qw = (Q + 3) / 4;
-    const int lgx = (width + GSR_BLOCK_X - 1) / GSR_BLOCK_X;
-    const bool no_hist = rankp && gsr::rank_direct(lgx, (int)tiles);   // no per-workgroup tile histograms: L2 atomics
+    const bool no_hist = rankp && gsr::rank_direct(tg.gx, (int)tiles);   // no per-workgroup tile histograms: L2 atomics
     size_t off = align_up(sizeof(gsr::BinHeader), A);  // header + statistics slots (gsr_device.h: BinHeader)
     o->keys = off;        off = align_up(off + (rankp && lists ? cap * 8 : 0), A);
     o->point_list = off;  off = align_up(off + (rankp ? cap * 4 : 0), A);
@@ -362,7 +388,7 @@ int gsr_binning_layout(int64_t capacity, int32_t width, int32_t height, int32_t 
     o->qmask = off;       off = align_up(off + (prod ? n * GSR_WALK_MASKS * 8 : 0), A);
     o->ranks = off;       off = align_up(off + (rankp ? cap * 8 : 0), A);
     int band_rows = 1;
-    const size_t nbands = rankp ? (size_t)gsr::rank_bands((long long)P, (int)(tiles / (size_t)lgx), tile_culling == 6, &band_rows) : 1;
+    const size_t nbands = rankp ? (size_t)gsr::rank_bands((long long)P, tg.gy, tile_culling == 6, &band_rows) : 1;
     const size_t nwc = (n + GSR_RANK_BAND_CHUNK - 1) / GSR_RANK_BAND_CHUNK;
     const bool bands = rankp && nbands > 1;
     o->rank = off;        off = align_up(off + (rankp ? n * (bands ? 16 : 4) : 0), A);
@@ -371,7 +397,7 @@ int gsr_binning_layout(int64_t capacity, int32_t width, int32_t height, int32_t 
     o->bandcnt = off;     off = align_up(off + (bands ? nbands * nwc * 4 : 0), A);
     o->srect = off;       off = align_up(off + (rankp ? n * 8 : 0), A);
     o->sspan = off;       off = align_up(off + (rankp ? n * 32 : 0), A);
-    o->pstat = off;       off = align_up(off + (rankp ? ((n + 255) / 256) * 80 + (GSR_RANK_BLOCKS + 4) * 4 : 0), A);   // (stats, four planes of group sums, k_rcount's chunk boundaries)
+    o->pstat = off;       off = align_up(off + (rankp ? pstat_bytes(splat_blocks(n)) : 0), A);
     o->tdesc = off;       off = align_up(off + (rankp ? tiles * 16 : 0), A);
     o->path = (size_t)path;
     o->chunks = chunks;
@@ -393,8 +419,7 @@ int gsr_image_layout(int32_t width, int32_t height, GsrImageLayout* o)
     o->c_final = off;   off = align_up(off + hw * 12, A);
     o->ck = off;        off = align_up(off + hw * 16 * (GSR_BWD_SEGMENTS - 1), A);
     o->gmax = off;      off = align_up(off + 4, A);
-    const size_t tiles = (size_t)((width + GSR_BLOCK_X - 1) / GSR_BLOCK_X) * (size_t)((height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y);
-    o->units = off;     off = align_up(off + gsr::unit_lists_words(tiles) * 4, A);
+    o->units = off;     off = align_up(off + gsr::unit_lists_words(tile_grid(width, height).tiles) * 4, A);
     o->total = off + A;
     return 0;
 }
@@ -417,350 +442,266 @@ static int to_bound(const GsrBound* b, int32_t P, bool backward, gsr::BoundDev* 
     return 0;
 }
 
-static int forward_impl(const GsrSettings* settings, int32_t P, int32_t M, const float* means3D, const float* shs, const float* shs_rest,
-                        const float* colors_precomp, const float* opacities, const float* scales, const float* rotations,
-                        const float* cov3D_precomp, float* out_color, int32_t* radii, void* geom, void* binning,
-                        int64_t binning_capacity, void* img, int64_t* num_rendered_host, void* stream_, const GsrBound* bound)
+// One forward on the stack of forward_impl: what its steps share
+struct Frame : StateViews {
+    hipStream_t stream;
+    bool dbg;
+    int P, pblocks, tiles;
+    gsr::Settings ds;
+    unsigned long long cap;                  // the caller's binning capacity
+    unsigned long long seq, post_cap;        // the post of the instance count: (seq << 40 | I) into *slot_dev
+    const unsigned long long* slot;          // ... as the host reads it
+    unsigned long long* slot_dev;
+    int rank_ilv;                            // rank path: rank_chunking
+};
+
+static int check_forward_args(const GsrSettings* settings, const gsr::PreprocessArgs& a, const float* out_color, const void* geom, const void* binning,
+                              int64_t binning_capacity, const void* img, const int64_t* num_rendered_host)
 {
     if (int rc = check_settings(settings)) return rc;
-    hipStream_t stream = (hipStream_t)stream_;
+    const int P = a.P, M = a.M;
     if (P < 0) return fail(GSR_E_ARG, "P must be >= 0");
     if ((long long)P * 48 > 0xFFFFFFFFll) return fail(GSR_E_ARG, "P = %d exceeds 89478485 splats: the blend addresses the 48-byte per-splat records with 32-bit offsets", P);
     if (!out_color || !num_rendered_host) return fail(GSR_E_ARG, "out_color / num_rendered_host is NULL");
     if (P > 0) {   // with no splats there is nothing to point at: empty tensors legitimately arrive as NULL
-        if ((shs == nullptr) == (colors_precomp == nullptr))
+        if ((a.shs == nullptr) == (a.colors_precomp == nullptr))
             return fail(GSR_E_ARG, "Please provide excatly one of either SHs or precomputed colors!");
-        const bool has_sr = scales != nullptr && rotations != nullptr;
-        if (((scales == nullptr) != (rotations == nullptr)) || (has_sr == (cov3D_precomp != nullptr)))
+        const bool has_sr = a.scales != nullptr && a.rotations != nullptr;
+        if (((a.scales == nullptr) != (a.rotations == nullptr)) || (has_sr == (a.cov3D_precomp != nullptr)))
             return fail(GSR_E_ARG, "Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!");
     }
-    if (shs_rest && (!shs || M < 2 || M > 16)) return fail(GSR_E_ARG, "split SH needs shs (P,1,3) + shs_rest (P,M-1,3) with 2 <= M <= 16");
-    if (shs && M < (settings->sh_degree + 1) * (settings->sh_degree + 1))
+    if (a.shs_rest && (!a.shs || M < 2 || M > 16)) return fail(GSR_E_ARG, "split SH needs shs (P,1,3) + shs_rest (P,M-1,3) with 2 <= M <= 16");
+    if (a.shs && M < (settings->sh_degree + 1) * (settings->sh_degree + 1))
         return fail(GSR_E_ARG, "shs has %d coefficients per splat but sh_degree %d needs %d", M, settings->sh_degree,
                     (settings->sh_degree + 1) * (settings->sh_degree + 1));
-    if (P > 0 && (!means3D || !opacities || !radii || !geom)) return fail(GSR_E_ARG, "NULL splat buffer");
+    if (P > 0 && (!a.means3D || !a.opacities || !a.radii || !geom)) return fail(GSR_E_ARG, "NULL splat buffer");
     if (!binning || !img) return fail(GSR_E_ARG, "NULL state buffer");
     if (binning_capacity < 0 || binning_capacity >= (1ll << 32)) return fail(GSR_E_ARG, "binning_capacity out of range");
-    {   // the rank path addresses the four quadrant streams of a tile as 32-bit ELEMENT offsets 4 * start + q * n into qpos
-        GsrBinningLayout probe;
-        gsr_binning_layout(0, settings->image_width, settings->image_height, P, settings->tile_culling, &probe);
-        if (probe.path != 1 && binning_capacity > (1ll << 30))
-            return fail(GSR_E_ARG, "binning_capacity %lld exceeds 2^30 tile instances (32-bit quadrant-stream offsets on this binning path)", (long long)binning_capacity);
-    }
+    return 0;
+}
 
-    const int W = settings->image_width, H = settings->image_height;
-    const int gx = (W + GSR_BLOCK_X - 1) / GSR_BLOCK_X, gy = (H + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y;
-    const int tiles = gx * gy;
-    const bool dbg = settings->debug != 0;
-    if (int rc = g_mail.init()) return rc;
-
-    GsrGeomLayout gl;
-    GsrBinningLayout bl;
-    GsrImageLayout il;
-    gsr_geom_layout(P, &gl);
-    gsr_binning_layout(binning_capacity, W, H, P, settings->tile_culling, &bl);
-    gsr_image_layout(W, H, &il);
-    char* g = (char*)geom;
-    char* b = (char*)binning;
-    char* im = (char*)img;
-    unsigned long long* total_dev = (unsigned long long*)b;
-    gsr::BinHeader* hdr = (gsr::BinHeader*)b;
-    uint32_t* tile_count = (uint32_t*)(b + bl.tile_count);
-    unsigned long long* rect_total = total_dev + 1;   // header word 1: sum of tiles_touched (the reference's num_rendered)
-    const bool prod = bl.path == 1;                   // depth-ordered scatter into the quadrant streams (gsr_binning.hip)
-
-    gsr::Settings ds = to_dev_settings(settings);
-    ds.fast_blend = fast_effective(settings) ? 1 : 0;
+// the header / counter memsets and k_preprocess (`a` arrives with the caller's inputs filled in)
+static int enqueue_preprocess(const Frame& f, const GsrSettings* settings, gsr::PreprocessArgs& a, const GsrBound* bound)
+{
+    const bool prod = f.bl.path == 1;
     if (prod) {
-        HIP_TRY(hipMemsetAsync(hdr, 0, sizeof(gsr::BinHeader), stream));   // k_preprocess accumulates the frame statistics into it
-    } else if (P == 0) {   // otherwise k_preprocess zeroes both
-        HIP_TRY(hipMemsetAsync(tile_count, 0, (size_t)tiles * 4, stream));
-        HIP_TRY(hipMemsetAsync(rect_total, 0, 8, stream));
-        HIP_TRY(hipMemsetAsync(im + il.units, 0, (size_t)32 * GSR_UNIT_LISTS * 4, stream));
+        HIP_TRY(hipMemsetAsync(f.b.hdr, 0, sizeof(gsr::BinHeader), f.stream));   // k_preprocess accumulates the frame statistics into it
+    } else if (f.P == 0) {   // otherwise k_preprocess zeroes both
+        HIP_TRY(hipMemsetAsync(f.b.tile_count, 0, (size_t)f.tiles * 4, f.stream));
+        HIP_TRY(hipMemsetAsync(f.b.rect_total, 0, 8, f.stream));
+        HIP_TRY(hipMemsetAsync(f.im.units, 0, (size_t)32 * GSR_UNIT_LISTS * 4, f.stream));
     }
-
-    gsr::PreprocessArgs pa;
-    pa.P = P; pa.M = M;
-    pa.means3D = means3D; pa.shs = shs; pa.shs_rest = shs_rest; pa.colors_precomp = colors_precomp; pa.opacities = opacities;
-    pa.scales = scales; pa.rotations = rotations; pa.cov3D_precomp = cov3D_precomp;
-    pa.radii = radii;
-    pa.depths = (float*)(g + gl.depths);
-    pa.grec = (float4*)(g + gl.grec);
-    pa.cov3D = (float*)(g + gl.cov3D);
-    pa.rect = (ushort4*)(g + gl.rect);
-    pa.tiles_touched = (uint32_t*)(g + gl.tiles_touched);
-    pa.clamped = (uint8_t*)(g + gl.clamped);
-    pa.visible = (uint8_t*)(g + gl.visible);
-    pa.acc = (float4*)(g + gl.acc);
-    pa.acc64 = (float4*)(g + gl.acc64);
+    a.depths = f.g.depths; a.grec = f.g.grec; a.cov3D = f.g.cov3D; a.rect = f.g.rect; a.tiles_touched = f.g.tiles_touched;
+    a.clamped = f.g.clamped; a.visible = f.g.visible; a.acc = f.g.acc; a.acc64 = f.g.acc64;
     // d colour / d view direction for the backward: only where a backward that reads it can follow (cfg2 / cfg5-style frames pay nothing)
-    pa.shjac = gsr::sh_jac_stashed(settings->forward_only != 0, colors_precomp != nullptr, M) && shs ? (float*)(g + gl.shjac) : nullptr;
-    pa.tile_count = tile_count;
-    pa.units = (uint32_t*)(im + il.units);
-    pa.rect_total = rect_total;
-    pa.tiles = tiles;
-    pa.brec = prod ? (float4*)(g + gl.brec) : nullptr;
-    pa.hdr = hdr;
-    pa.bcount = (uint32_t*)(b + bl.bcount);
-    pa.nb = (int)bl.nb;
-    const bool rankp = bl.path == 0;                  // tiles ordered by global depth rank (gsr_rank.hip)
-    pa.bcursor = (uint32_t*)(b + bl.bcursor);
-    pa.pstat = rankp ? (uint4*)(b + bl.pstat) : nullptr;
-    pa.srect = (ushort4*)(b + bl.srect);
-    pa.sspan = (float4*)(b + bl.sspan);
-    pa.cull = settings->tile_culling != 0;
-    if (int rc = to_bound(bound, P, false, &pa.bound)) return rc;
-    const int pblocks = (P + 255) / 256;
-    if (pblocks > 0) {
-        TIMED(GSR_K_PREPROCESS, stream);
-        auto* const pre_k = pa.shjac ? &gsr::k_preprocess<true> : &gsr::k_preprocess<false>;
-        hipLaunchKernelGGL(pre_k, dim3(pblocks), dim3(256), 0, stream, ds, pa);
-        KERNEL_CHECK("k_preprocess", stream, dbg);
+    a.shjac = gsr::sh_jac_stashed(settings->forward_only != 0, a.colors_precomp != nullptr, a.M) && a.shs ? f.g.shjac : nullptr;
+    a.tile_count = f.b.tile_count; a.units = f.im.units; a.rect_total = f.b.rect_total; a.tiles = f.tiles;
+    a.brec = f.g.brec; a.hdr = f.b.hdr; a.bcount = f.b.bcount; a.nb = (int)f.bl.nb;
+    a.bcursor = f.b.bcursor; a.pstat = f.b.pstat; a.srect = f.b.srect; a.sspan = f.b.sspan;
+    a.cull = settings->tile_culling != 0;
+    if (int rc = to_bound(bound, f.P, false, &a.bound)) return rc;
+    if (f.pblocks > 0) {
+        TIMED(GSR_K_PREPROCESS, f.stream);
+        auto* const pre_k = a.shjac ? &gsr::k_preprocess<true> : &gsr::k_preprocess<false>;
+        hipLaunchKernelGGL(pre_k, dim3(f.pblocks), dim3(256), 0, f.stream, f.ds, a);
+        KERNEL_CHECK("k_preprocess", f.stream, f.dbg);
     }
+    return 0;
+}
 
-    const unsigned long long seq = (g_mail.seq.fetch_add(1) % 0xFFFFFEull) + 1;  // 1 .. 2^24-2, never 0
-    g_last_seq = (long long)seq;
-    // where the scan posts (seq, I): a ring slot this call spins on, or -- deferred count -- the caller's persistent slot, read
-    // later through gsr_count_slot_read (nothing waits, so the call can sit inside a stream capture and be replayed as a hipGraph)
-    const bool deferred = settings->deferred_count != 0;
-    const size_t slot_index = deferred ? (size_t)Mailbox::kSlots + (size_t)(settings->deferred_count - 1) : (size_t)(seq % Mailbox::kSlots);
-    volatile unsigned long long* slot = g_mail.host + slot_index;
-    *slot = 0;   // (a persistent slot may still hold what its previous owner's last frame posted)
-    unsigned long long* slot_dev = g_mail.dev + slot_index;
-    const unsigned long long post_cap = deferred ? (unsigned long long)binning_capacity : ~0ull;   // deferred: an overflowing frame marks the slot's sticky word
-    // rank path: contiguous chunks of splats per workgroup, or -- when the previous frame of this (device, size) reported its tile instances unevenly spread
-    // along the splat order -- small groups dealt round-robin (gsr_device.h: rank_chunk / rank_splat; this frame's own report rides in the posted count)
-    int dev_id = 0, rank_ilv = -1;
+// Where the scan posts (seq, I): a ring slot this call spins on, or -- deferred count -- the caller's persistent slot, read later through
+// gsr_count_slot_read (nothing waits, so the call can sit inside a stream capture and be replayed as a hipGraph).  And, as the post carries
+// the rank path's report of this frame, how the rank path chunks its passes after the previous frame's report.
+static int open_post(Frame& f, const GsrSettings* settings)
+{
+    f.seq = (g_mail.seq.fetch_add(1) % 0xFFFFFEull) + 1;  // 1 .. 2^24-2, never 0
+    g_last_seq = (long long)f.seq;
+    const bool deferred = settings->deferred_count != 0, rankp = f.bl.path == 0;
+    const size_t slot_index = deferred ? (size_t)Mailbox::kSlots + (size_t)(settings->deferred_count - 1) : (size_t)(f.seq % Mailbox::kSlots);
+    *(volatile unsigned long long*)(g_mail.host + slot_index) = 0;   // (a persistent slot may still hold what its previous owner's last frame posted)
+    f.slot = g_mail.host + slot_index;
+    f.slot_dev = g_mail.dev + slot_index;
+    f.post_cap = deferred ? f.cap : ~0ull;   // deferred: an overflowing frame marks the slot's sticky word
+    int dev_id = 0;
+    f.rank_ilv = -1;
     if (rankp) {
         HIP_TRY(hipGetDevice(&dev_id));
-        const int ilv = rank_ilv_for(dev_id, settings->image_width, settings->image_height);   // 0: contiguous, else a group size (rounded down to a power of two)
-        rank_ilv = -1;
-        for (int v = ilv; v > 0; v >>= 1) ++rank_ilv;                                                // log2, -1 for contiguous
-        // ... and on frames of one band the answer to an uneven spread is not the interleave but contiguous chunks of equal WEIGHT, cut by k_rcount from
-        // k_preprocess's group sums (gsr_device.h: rank_map; round 6): the template-like head's scatter 44 -> 31 us where the interleave had brought it from
-        // 88 to 44, and k_rcount keeps its compact set of tiles.  (It costs k_rcount 3.5 us of prologue, so an even frame keeps its equal-count chunks.)
-        // GSR_RANK_BALANCED=0: the interleave; =2: balanced chunks on every frame (A/B runs)
-        static const int balanced = [] { const char* e = getenv("GSR_RANK_BALANCED"); return e ? atoi(e) : 1; }();
-        static const bool forced_ilv = getenv("GSR_RANK_ILV") != nullptr;
-        const bool can = (long long)P <= (long long)GSR_RANK_MAX_SPLATS && (int)bl.nbands <= 1 && !forced_ilv;
-        if (can && ((balanced == 1 && ilv > 0) || balanced == 2)) rank_ilv = -2;
+        f.rank_ilv = rank_chunking(dev_id, settings->image_width, settings->image_height, f.P, (int)f.bl.nbands);
     }
     slot_holds_frame(deferred ? settings->deferred_count - 1 : GSR_COUNT_SLOTS, dev_id, rankp ? settings->image_width : 0, settings->image_height);
-    // Optimistic launch: the rest of the frame is enqueued against the caller's capacity before the
-    // host knows I; every kernel re-checks *total_dev <= capacity on the device and does nothing
-    // otherwise.  The host then waits only for the scan (early in the frame), not for the frame.
-    const unsigned long long cap = (unsigned long long)binning_capacity;
-    uint32_t* tile_order = (uint32_t*)(b + bl.tile_order);
-    uint32_t* qpos = (uint32_t*)(b + bl.qpos);
-    uint32_t* qcount = (uint32_t*)(b + bl.qcount);
-    uint32_t* qstart = (uint32_t*)(b + bl.qstart);
-    const bool write_lists = settings->tile_culling == 0 || settings->tile_culling == 2;   // production (1, 3, 4): the sorted key / point lists are not materialised
-    uint32_t* qlist = (uint32_t*)(b + bl.qlist);
+    return 0;
+}
 
-    if (prod) {
-        // ---- production: sort the SPLATS by depth, then append them in that order to the quadrant streams ----------------
-        const uint32_t nb = (uint32_t)bl.nb, chunks = (uint32_t)bl.chunks;
-        const int Q = 4 * tiles;
-        uint32_t* bcount = (uint32_t*)(b + bl.bcount);
-        uint32_t* bstart = (uint32_t*)(b + bl.bstart);
-        uint32_t* bcursor = (uint32_t*)(b + bl.bcursor);
-        uint32_t* border = (uint32_t*)(b + bl.border);
-        unsigned long long* dkeys = (unsigned long long*)(b + bl.dkeys);
-        unsigned long long* dtmp = (unsigned long long*)(b + bl.dtmp);
-        uint32_t* order = (uint32_t*)(b + bl.order);
-        const uint32_t* brec_rect = (const uint32_t*)(g + gl.brec);
-        {
-            TIMED(GSR_K_DEPTH_SORT, stream);
-            const int dblocks = pblocks < GSR_BIN_BLOCKS ? pblocks : GSR_BIN_BLOCKS;
-            uint32_t* bhist = (uint32_t*)(b + bl.bhist);
-            hipLaunchKernelGGL(gsr::k_dbucket, dim3(dblocks), dim3(256), (size_t)nb * 4, stream, P, brec_rect, (const float*)pa.depths, hdr, nb,
-                               bcount, bhist);
-            hipLaunchKernelGGL(gsr::k_dscan, dim3(1), dim3(1024), 0, stream, nb, (const uint32_t*)bcount, bstart, bcursor, border, hdr);
-            hipLaunchKernelGGL(gsr::k_dscatter, dim3(dblocks), dim3(256), (size_t)nb * 4, stream, P, brec_rect, (const float*)pa.depths,
-                               (const gsr::BinHeader*)hdr, nb, (const uint32_t*)bstart, bcursor, dkeys, (const uint32_t*)bhist);
-            // one class: 2048 keys in registers per workgroup, heavier buckets (rare: the bucket map is linear in this frame's own depth
-            // range) by chunked sorts + merges in global memory; heaviest buckets first
-            hipLaunchKernelGGL((gsr::k_dsort<GSR_SORT_SMALL_KEYS, 256>), dim3(nb), dim3(256), 0, stream, 0u, 0xFFFFFFFFu,
-                               (const uint32_t*)border, (const uint32_t*)bcount, (const uint32_t*)bstart, dkeys, dtmp, order);
-            KERNEL_CHECK("depth sort", stream, dbg);
-        }
-        gsr::QBinArgs qa;
-        qa.Q = Q; qa.gx = gx; qa.chunks = chunks;
-        qa.qmask = (unsigned long long*)(b + bl.qmask);
-        qa.hdr = hdr; qa.brec = (const float4*)(g + gl.brec); qa.order = order;
-        qa.qhist = (uint32_t*)(b + bl.qhist); qa.qprefix = (const uint32_t*)(b + bl.qprefix); qa.qstart = qstart; qa.qpos = qpos;
-        qa.capacity = cap;
-        const size_t count_lds = (((size_t)Q + 3) / 4) * 4;   // byte counters, four to a word
-        const size_t walk_lds = (size_t)Q * 4;               // absolute cursors
-        if (walk_lds > 48 * 1024)
-            if (int rc = ensure_dynamic_lds((const void*)gsr::k_qscatter, (size_t)walk_lds)) return rc;
-        const int walk_blocks = (int)chunks;   // one workgroup per chunk, one wave per band
-        {
-            TIMED(GSR_K_QCOUNT, stream);
-            hipLaunchKernelGGL(gsr::k_qcount, dim3(walk_blocks), dim3(256), count_lds, stream, qa);
-            KERNEL_CHECK("k_qcount", stream, dbg);
-        }
-        {
-            TIMED(GSR_K_QSCAN, stream);
-            hipLaunchKernelGGL(gsr::k_qscan, dim3(((Q + 3) / 4 + 31) / 32), dim3(1024), 0, stream, Q, chunks, (const uint8_t*)(b + bl.qhist),
-                               (uint32_t*)(b + bl.qprefix), qcount);
-            hipLaunchKernelGGL(gsr::k_qscan_glob, dim3(1), dim3(1024), 0, stream, tiles, (const uint32_t*)qcount, qstart, tile_order, hdr,
-                               slot_dev, seq, post_cap);
-            KERNEL_CHECK("k_qscan", stream, dbg);
-        }
-        {
-            TIMED(GSR_K_QSCATTER, stream);
-            hipLaunchKernelGGL(gsr::k_qscatter, dim3(walk_blocks), dim3(64), walk_lds, stream, qa);
-            KERNEL_CHECK("k_qscatter", stream, dbg);
-        }
-    } else {
-        // ---- rank path: depth-rank the splats once, order every tile's instances through an LDS bitmap (gsr_rank.hip) ----
-        const uint32_t nb = (uint32_t)bl.nb;
-        const int bin_blocks = pblocks < GSR_RANK_BLOCKS ? pblocks : GSR_RANK_BLOCKS;
-        const bool direct = gsr::rank_direct(gx, tiles);
-        uint32_t* const chunk_bounds = reinterpret_cast<uint32_t*>((uint4*)(b + bl.pstat) + 5 * (size_t)pblocks);   // behind pstat's rows and the four planes of group sums
-        const size_t hist_bytes = direct ? 0 : (size_t)tiles * sizeof(uint32_t);
-        const size_t count_lds = (size_t)nb * 4 + (direct ? 0 : (size_t)(gx + 1) * (size_t)(gy + 1) * sizeof(uint32_t));   // corner grid of the tile rects
-        if (count_lds > 48 * 1024) {
-            if (int rc = ensure_dynamic_lds((const void*)gsr::k_rcount, (size_t)count_lds)) return rc;
-        }
-        // the scatter's dynamic LDS: the tile histogram, then (when they fit the 160 KB beside it and the sort's 16 KB of keys) the staging
-        // rows of the balanced expansion (else: the lockstep form)
-        const bool one_band_lds = (int)bl.nbands <= 1;
-        const size_t stage_bytes = GSR_RSCATTER_STAGE_BYTES(one_band_lds), hist_al = (hist_bytes + 15) & ~(size_t)15;
-        const bool balanced = hist_al + stage_bytes + 20 * 1024 <= 160 * 1024;
-        const int stage_off = balanced ? (int)hist_al : -1;
-        const size_t scatter_lds = balanced ? hist_al + stage_bytes : hist_bytes;
-        if (scatter_lds > 48 * 1024)
-        {
-            if (int rc = ensure_dynamic_lds((const void*)gsr::k_rsort_rscatter, scatter_lds)) return rc;
-            if (int rc = ensure_dynamic_lds((const void*)gsr::k_rscatter<8>, scatter_lds)) return rc;
-        }
-        uint32_t* block_hist = (uint32_t*)(b + bl.block_hist);
-        uint32_t* bcount = (uint32_t*)(b + bl.bcount);
-        uint32_t* bstart = (uint32_t*)(b + bl.bstart);
-        uint32_t* bcursor = (uint32_t*)(b + bl.bcursor);
-        uint32_t* bhist = (uint32_t*)(b + bl.bhist);
-        unsigned long long* dkeys = (unsigned long long*)(b + bl.dkeys);
-        unsigned long long* dtmp = (unsigned long long*)(b + bl.dtmp);
-        uint32_t* rank = (uint32_t*)(b + bl.rank);
-        uint2* ranks = (uint2*)(b + bl.ranks);
-        const int nbands = (int)bl.nbands;
-        const float inv_band_rows = 1.0f / (float)bl.band_rows;
-        uint2* obs = nbands > 1 ? (uint2*)(b + bl.obs) : nullptr;
-        uint32_t* bandcnt = (uint32_t*)(b + bl.bandcnt);
-        const uint32_t nwc = (uint32_t)(((size_t)P + GSR_RANK_BAND_CHUNK - 1) / GSR_RANK_BAND_CHUNK);
-        gsr::BandTables bt;
-        bt.nbands = (uint32_t)nbands;
-        bt.inv_band_rows = inv_band_rows;
-        bt.over = (const uint32_t*)(b + bl.rank_over);
-        ushort4* srect = (ushort4*)(b + bl.srect);
-        uint32_t* tile_start = (uint32_t*)(b + bl.tile_start);
-        uint32_t* tile_cursor = (uint32_t*)(b + bl.tile_cursor);
-        uint2* ranges = (uint2*)(b + bl.ranges);
-        if (pblocks > 0) {
-            TIMED(GSR_K_COUNT, stream);
-            hipLaunchKernelGGL(gsr::k_rcount, dim3(bin_blocks), dim3(GSR_RANK_BIN_THREADS), count_lds, stream, rank_ilv, P, gx, tiles,
-                               pblocks, nb, (const ushort4*)srect, (const uint32_t*)pa.tiles_touched,
-                               (const float*)pa.depths, (const uint4*)pa.pstat, tile_count, rect_total, block_hist, bcount, bhist, hdr, chunk_bounds);
-            KERNEL_CHECK("k_rcount", stream, dbg);
-        }
-        const bool one_band = nbands <= 1;
-        {
-            TIMED(GSR_K_DEPTH_SORT, stream);
-            // the depth keys into their buckets; the last workgroup scans the tile counters and posts the instance count (launched even when P == 0)
-            gsr::TileScanArgs ts;
-            ts.tiles = tiles; ts.tile_count = tile_count; ts.tile_start = tile_start; ts.tile_cursor = tile_cursor; ts.ranges = ranges;
-            ts.tile_order = tile_order; ts.tdesc = (uint4*)(b + bl.tdesc); ts.total_dev = total_dev; ts.mailbox = slot_dev; ts.seq = seq;
-            ts.post_capacity = post_cap;
-            ts.hdr = pblocks > 0 ? hdr : nullptr;   // (P == 0: k_rcount did not run, the header word is not written)
-            hipLaunchKernelGGL(gsr::k_rdscatter, dim3((pblocks > 0 ? bin_blocks : 0) + 1), dim3(GSR_RANK_BIN_THREADS), (size_t)nb * 4, stream, rank_ilv, P, nb,
-                               (const ushort4*)srect, (const float*)pa.depths, hdr, (const uint32_t*)bcount, bstart, bcursor, dkeys, (const uint32_t*)bhist, ts,
-                               (const uint32_t*)chunk_bounds);
-            KERNEL_CHECK("k_rdscatter", stream, dbg);
-            if (!one_band && pblocks > 0) {
-                // large frames: a rank per (splat, band of tile rows) -- see gsr_rank.hip
-                hipLaunchKernelGGL(gsr::k_rdsort, dim3(nb), dim3(256), 0, stream, (const uint32_t*)bcount, (const uint32_t*)bstart, dkeys, dtmp, rank, obs,
-                                   (const ushort4*)srect, (int)bl.band_rows);
-                KERNEL_CHECK("k_rdsort", stream, dbg);
-                const uint32_t wgs = (nwc + 3u) / 4u;
-                hipLaunchKernelGGL(gsr::k_band_count, dim3(wgs), dim3(256), 0, stream, (const gsr::BinHeader*)hdr, (const uint2*)obs,
-                                   (uint32_t)nbands, nwc, bandcnt);
-                hipLaunchKernelGGL(gsr::k_band_scan, dim3(nbands), dim3(1024), 0, stream, hdr, nwc, bandcnt);
-                hipLaunchKernelGGL(gsr::k_band_rank, dim3(wgs), dim3(256), 0, stream, (const gsr::BinHeader*)hdr, (const uint2*)obs,
-                                   (uint32_t)nbands, nwc, (const uint32_t*)bandcnt, (uint4*)rank, (uint32_t*)(b + bl.rank_over));
-                KERNEL_CHECK("k_band_rank", stream, dbg);
-            }
-        }
-        if (pblocks > 0) {
-            TIMED(GSR_K_SCATTER, stream);
-            if (one_band) {   // the depth sort beside the scatter, one launch (k_rsort_rscatter): 4-byte entries, k_tile_rank gathers the ranks
-                hipLaunchKernelGGL(gsr::k_rsort_rscatter, dim3(bin_blocks + nb), dim3(GSR_RANK_BIN_THREADS), scatter_lds, stream, rank_ilv, bin_blocks, P, gx, tiles,
-                                   (const ushort4*)srect, (const float4*)pa.sspan, (const uint32_t*)tile_start, tile_cursor, (uint32_t*)ranks, cap,
-                                   (const unsigned long long*)total_dev, (const uint32_t*)block_hist, (const uint32_t*)bcount, (const uint32_t*)bstart,
-                                   dkeys, dtmp, rank, stage_off, (const uint32_t*)chunk_bounds);
-                KERNEL_CHECK("k_rsort_rscatter", stream, dbg);
-            } else {
-                hipLaunchKernelGGL(gsr::k_rscatter<8>, dim3(bin_blocks), dim3(GSR_RANK_BIN_THREADS), scatter_lds, stream, rank_ilv, P, gx, tiles, bt,
-                                   (const ushort4*)srect, (const uint32_t*)rank, (const float4*)pa.sspan, (const uint32_t*)tile_start, tile_cursor, ranks, cap,
-                                   (const unsigned long long*)total_dev, (const uint32_t*)block_hist, stage_off, (const uint32_t*)chunk_bounds);
-                KERNEL_CHECK("k_rscatter", stream, dbg);
-            }
-        }
-        {
-            TIMED(GSR_K_TILE_SORT, stream);
-            // the bitmap holds a rank space (the frame's, or a band's) in one pass unless it exceeds GSR_RANK_MAX_SPLATS splats (then: several)
-            const size_t space = (size_t)P < (size_t)GSR_RANK_MAX_SPLATS ? (size_t)P : (size_t)GSR_RANK_MAX_SPLATS;
-            const uint32_t words = (uint32_t)((space + 2047) / 2048) * 64u;
-            hipLaunchKernelGGL(gsr::k_tile_rank, dim3(tiles), dim3(GSR_RANK_TILE_THREADS), (size_t)words * 6, stream, words, gx, nbands,
-                               inv_band_rows, (const uint4*)(b + bl.tdesc), (const uint2*)ranks, one_band ? (const uint32_t*)rank : nullptr, (const float*)pa.depths,
-                               (const gsr::BinHeader*)hdr, write_lists ? (unsigned long long*)(b + bl.keys) : nullptr,
-                               (uint32_t*)(b + bl.point_list), write_lists ? qlist : nullptr, qpos, qcount, qstart,
-                               cap, (const unsigned long long*)total_dev);
-            KERNEL_CHECK("k_tile_rank", stream, dbg);
+// ---- production: sort the SPLATS by depth, then append them in that order to the quadrant streams (gsr_binning.hip) ----------------
+static int enqueue_scatter_binning(const Frame& f)
+{
+    const BinView& b = f.b;
+    hipStream_t stream = f.stream;
+    const uint32_t nb = (uint32_t)f.bl.nb, chunks = (uint32_t)f.bl.chunks;
+    const int P = f.P, Q = 4 * f.tiles;
+    const uint32_t* brec_rect = reinterpret_cast<const uint32_t*>(f.g.brec);
+    {
+        TIMED(GSR_K_DEPTH_SORT, stream);
+        const int dblocks = f.pblocks < GSR_BIN_BLOCKS ? f.pblocks : GSR_BIN_BLOCKS;
+        hipLaunchKernelGGL(gsr::k_dbucket, dim3(dblocks), dim3(256), (size_t)nb * 4, stream, P, brec_rect, f.g.depths, b.hdr, nb, b.bcount, b.bhist);
+        hipLaunchKernelGGL(gsr::k_dscan, dim3(1), dim3(1024), 0, stream, nb, b.bcount, b.bstart, b.bcursor, b.border, b.hdr);
+        hipLaunchKernelGGL(gsr::k_dscatter, dim3(dblocks), dim3(256), (size_t)nb * 4, stream, P, brec_rect, f.g.depths, b.hdr, nb, b.bstart, b.bcursor,
+                           b.dkeys, b.bhist);
+        // one class: 2048 keys in registers per workgroup, heavier buckets (rare: the bucket map is linear in this frame's own depth
+        // range) by chunked sorts + merges in global memory; heaviest buckets first
+        hipLaunchKernelGGL((gsr::k_dsort<GSR_SORT_SMALL_KEYS, 256>), dim3(nb), dim3(256), 0, stream, 0u, 0xFFFFFFFFu, b.border, b.bcount, b.bstart,
+                           b.dkeys, b.dtmp, b.order);
+        KERNEL_CHECK("depth sort", stream, f.dbg);
+    }
+    gsr::QBinArgs qa;
+    qa.Q = Q; qa.gx = f.tg.gx; qa.chunks = chunks;
+    qa.qmask = b.qmask;
+    qa.hdr = b.hdr; qa.brec = f.g.brec; qa.order = b.order;
+    qa.qhist = b.qhist; qa.qprefix = b.qprefix; qa.qstart = b.qstart; qa.qpos = b.qpos;
+    qa.capacity = f.cap;
+    const size_t count_lds = (((size_t)Q + 3) / 4) * 4;   // byte counters, four to a word
+    const size_t walk_lds = (size_t)Q * 4;               // absolute cursors
+    if (walk_lds > 48 * 1024)
+        if (int rc = ensure_dynamic_lds((const void*)gsr::k_qscatter, (size_t)walk_lds)) return rc;
+    const int walk_blocks = (int)chunks;   // one workgroup per chunk, one wave per band
+    {
+        TIMED(GSR_K_QCOUNT, stream);
+        hipLaunchKernelGGL(gsr::k_qcount, dim3(walk_blocks), dim3(256), count_lds, stream, qa);
+        KERNEL_CHECK("k_qcount", stream, f.dbg);
+    }
+    {
+        TIMED(GSR_K_QSCAN, stream);
+        hipLaunchKernelGGL(gsr::k_qscan, dim3(((Q + 3) / 4 + 31) / 32), dim3(1024), 0, stream, Q, chunks, reinterpret_cast<const uint8_t*>(b.qhist),
+                           b.qprefix, b.qcount);
+        hipLaunchKernelGGL(gsr::k_qscan_glob, dim3(1), dim3(1024), 0, stream, f.tiles, b.qcount, b.qstart, b.tile_order, b.hdr, f.slot_dev, f.seq,
+                           f.post_cap);
+        KERNEL_CHECK("k_qscan", stream, f.dbg);
+    }
+    {
+        TIMED(GSR_K_QSCATTER, stream);
+        hipLaunchKernelGGL(gsr::k_qscatter, dim3(walk_blocks), dim3(64), walk_lds, stream, qa);
+        KERNEL_CHECK("k_qscatter", stream, f.dbg);
+    }
+    return 0;
+}
+
+// the rank path's scatter and the dynamic LDS it takes: the tile histogram, then (when they fit the 160 KB beside it and the sort's 16 KB of
+// keys) the staging rows of the balanced expansion (else: the lockstep form, stage_off -1)
+struct RankScatterLds { size_t bytes; int stage_off; };
+static RankScatterLds rank_scatter_lds(bool direct, int tiles, bool one_band)
+{
+    const size_t hist_bytes = direct ? 0 : (size_t)tiles * sizeof(uint32_t);
+    const size_t stage_bytes = GSR_RSCATTER_STAGE_BYTES(one_band), hist_al = (hist_bytes + 15) & ~(size_t)15;
+    const bool balanced = hist_al + stage_bytes + 20 * 1024 <= 160 * 1024;
+    return {balanced ? hist_al + stage_bytes : hist_bytes, balanced ? (int)hist_al : -1};
+}
+
+// large frames of the rank path: a rank per (splat, band of tile rows) -- see gsr_rank.hip
+static int enqueue_band_ranks(const Frame& f, uint32_t nb)
+{
+    const BinView& b = f.b;
+    const uint32_t nbands = (uint32_t)f.bl.nbands;
+    const uint32_t nwc = (uint32_t)(((size_t)f.P + GSR_RANK_BAND_CHUNK - 1) / GSR_RANK_BAND_CHUNK);
+    hipLaunchKernelGGL(gsr::k_rdsort, dim3(nb), dim3(256), 0, f.stream, b.bcount, b.bstart, b.dkeys, b.dtmp, b.rank, b.obs, b.srect, (int)f.bl.band_rows);
+    KERNEL_CHECK("k_rdsort", f.stream, f.dbg);
+    const uint32_t wgs = (nwc + 3u) / 4u;
+    hipLaunchKernelGGL(gsr::k_band_count, dim3(wgs), dim3(256), 0, f.stream, b.hdr, b.obs, nbands, nwc, b.bandcnt);
+    hipLaunchKernelGGL(gsr::k_band_scan, dim3(nbands), dim3(1024), 0, f.stream, b.hdr, nwc, b.bandcnt);
+    hipLaunchKernelGGL(gsr::k_band_rank, dim3(wgs), dim3(256), 0, f.stream, b.hdr, b.obs, nbands, nwc, b.bandcnt,
+                       reinterpret_cast<uint4*>(b.rank), b.rank_over);   // (with bands, `rank` holds 16 bytes per splat)
+    KERNEL_CHECK("k_band_rank", f.stream, f.dbg);
+    return 0;
+}
+
+// ---- rank path: depth-rank the splats once, order every tile's instances through an LDS bitmap (gsr_rank.hip) ----
+static int enqueue_rank_binning(const Frame& f)
+{
+    const BinView& b = f.b;
+    hipStream_t stream = f.stream;
+    const int P = f.P, pblocks = f.pblocks, gx = f.tg.gx, gy = f.tg.gy, tiles = f.tiles, rank_ilv = f.rank_ilv;
+    const uint32_t nb = (uint32_t)f.bl.nb;
+    const int bin_blocks = pblocks < GSR_RANK_BLOCKS ? pblocks : GSR_RANK_BLOCKS;
+    const bool direct = gsr::rank_direct(gx, tiles);
+    const size_t count_lds = (size_t)nb * 4 + (direct ? 0 : (size_t)(gx + 1) * (size_t)(gy + 1) * sizeof(uint32_t));   // corner grid of the tile rects
+    if (count_lds > 48 * 1024) {
+        if (int rc = ensure_dynamic_lds((const void*)gsr::k_rcount, (size_t)count_lds)) return rc;
+    }
+    const int nbands = (int)f.bl.nbands;
+    const bool one_band = nbands <= 1;
+    const RankScatterLds scatter = rank_scatter_lds(direct, tiles, one_band);
+    if (scatter.bytes > 48 * 1024)
+    {
+        if (int rc = ensure_dynamic_lds((const void*)gsr::k_rsort_rscatter, scatter.bytes)) return rc;
+        if (int rc = ensure_dynamic_lds((const void*)gsr::k_rscatter<8>, scatter.bytes)) return rc;
+    }
+    const float inv_band_rows = 1.0f / (float)f.bl.band_rows;
+    if (pblocks > 0) {
+        TIMED(GSR_K_COUNT, stream);
+        hipLaunchKernelGGL(gsr::k_rcount, dim3(bin_blocks), dim3(GSR_RANK_BIN_THREADS), count_lds, stream, rank_ilv, P, gx, tiles, pblocks, nb, b.srect,
+                           f.g.tiles_touched, f.g.depths, b.pstat, b.tile_count, b.rect_total, b.block_hist, b.bcount, b.bhist, b.hdr, b.chunk_bounds);
+        KERNEL_CHECK("k_rcount", stream, f.dbg);
+    }
+    {
+        TIMED(GSR_K_DEPTH_SORT, stream);
+        // the depth keys into their buckets; the last workgroup scans the tile counters and posts the instance count (launched even when P == 0)
+        gsr::TileScanArgs ts;
+        ts.tiles = tiles; ts.tile_count = b.tile_count; ts.tile_start = b.tile_start; ts.tile_cursor = b.tile_cursor; ts.ranges = b.ranges;
+        ts.tile_order = b.tile_order; ts.tdesc = b.tdesc; ts.total_dev = b.total; ts.mailbox = f.slot_dev; ts.seq = f.seq;
+        ts.post_capacity = f.post_cap;
+        ts.hdr = pblocks > 0 ? b.hdr : nullptr;   // (P == 0: k_rcount did not run, the header word is not written)
+        hipLaunchKernelGGL(gsr::k_rdscatter, dim3((pblocks > 0 ? bin_blocks : 0) + 1), dim3(GSR_RANK_BIN_THREADS), (size_t)nb * 4, stream, rank_ilv, P, nb,
+                           b.srect, f.g.depths, b.hdr, b.bcount, b.bstart, b.bcursor, b.dkeys, b.bhist, ts, b.chunk_bounds);
+        KERNEL_CHECK("k_rdscatter", stream, f.dbg);
+        if (!one_band && pblocks > 0)
+            if (int rc = enqueue_band_ranks(f, nb)) return rc;
+    }
+    if (pblocks > 0) {
+        TIMED(GSR_K_SCATTER, stream);
+        if (one_band) {   // the depth sort beside the scatter, one launch (k_rsort_rscatter): 4-byte entries, k_tile_rank gathers the ranks
+            hipLaunchKernelGGL(gsr::k_rsort_rscatter, dim3(bin_blocks + nb), dim3(GSR_RANK_BIN_THREADS), scatter.bytes, stream, rank_ilv, bin_blocks, P, gx, tiles,
+                               b.srect, b.sspan, b.tile_start, b.tile_cursor, reinterpret_cast<uint32_t*>(b.ranks), f.cap, b.total, b.block_hist, b.bcount,
+                               b.bstart, b.dkeys, b.dtmp, b.rank, scatter.stage_off, b.chunk_bounds);
+            KERNEL_CHECK("k_rsort_rscatter", stream, f.dbg);
+        } else {
+            gsr::BandTables bt;
+            bt.nbands = (uint32_t)nbands;
+            bt.inv_band_rows = inv_band_rows;
+            bt.over = b.rank_over;
+            hipLaunchKernelGGL(gsr::k_rscatter<8>, dim3(bin_blocks), dim3(GSR_RANK_BIN_THREADS), scatter.bytes, stream, rank_ilv, P, gx, tiles, bt, b.srect,
+                               b.rank, b.sspan, b.tile_start, b.tile_cursor, b.ranks, f.cap, b.total, b.block_hist, scatter.stage_off, b.chunk_bounds);
+            KERNEL_CHECK("k_rscatter", stream, f.dbg);
         }
     }
     {
-        TIMED(GSR_K_RENDER, stream);
-        const bool infer = ds.forward_only;   // (torch.no_grad() / fps benchmarks: the instances without the backward's bookkeeping)
-        auto* const render_k = !ds.fast_blend ? (infer ? &gsr::k_render<false, true> : &gsr::k_render<false, false>)
-                                              : (infer ? &gsr::k_render<true, true> : &gsr::k_render<true, false>);
-        // one wave per workgroup, four workgroups per tile (gsr_forward.hip)
-        hipLaunchKernelGGL(render_k, dim3(4 * tiles), dim3(64), 0, stream, ds, (const uint32_t*)tile_order, (const uint32_t*)qstart,
-                           (const uint32_t*)qcount, (const float4*)pa.grec, (const uint32_t*)qpos, write_lists ? (const uint32_t*)qlist : nullptr, (float*)(im + il.final_T), (uint32_t*)(im + il.n_contrib),
-                           (uint32_t*)(im + il.n_contrib_q), (float*)(im + il.c_final), (float4*)(im + il.ck), out_color, cap,
-                           (const unsigned long long*)total_dev, (uint32_t*)(im + il.units), tiles);
-        KERNEL_CHECK("k_render", stream, dbg);
+        TIMED(GSR_K_TILE_SORT, stream);
+        // the bitmap holds a rank space (the frame's, or a band's) in one pass unless it exceeds GSR_RANK_MAX_SPLATS splats (then: several)
+        const size_t space = (size_t)P < (size_t)GSR_RANK_MAX_SPLATS ? (size_t)P : (size_t)GSR_RANK_MAX_SPLATS;
+        const uint32_t words = (uint32_t)((space + 2047) / 2048) * 64u;
+        hipLaunchKernelGGL(gsr::k_tile_rank, dim3(tiles), dim3(GSR_RANK_TILE_THREADS), (size_t)words * 6, stream, words, gx, nbands, inv_band_rows, b.tdesc,
+                           b.ranks, one_band ? b.rank : nullptr, f.g.depths, b.hdr, b.keys, b.point_list, b.qlist, b.qpos, b.qcount, b.qstart, f.cap, b.total);
+        KERNEL_CHECK("k_tile_rank", stream, f.dbg);
     }
+    return 0;
+}
 
-    if (deferred) {   // the count of this frame is not known yet: the caller checks its slot after the fact
-        *num_rendered_host = -1;
-        return GSR_OK;
-    }
-    // wait for the scan's post
-    const auto t0 = std::chrono::steady_clock::now();
+static int enqueue_render(const Frame& f, float* out_color)
+{
+    TIMED(GSR_K_RENDER, f.stream);
+    const bool infer = f.ds.forward_only;   // (torch.no_grad() / fps benchmarks: the instances without the backward's bookkeeping)
+    auto* const render_k = !f.ds.fast_blend ? (infer ? &gsr::k_render<false, true> : &gsr::k_render<false, false>)
+                                            : (infer ? &gsr::k_render<true, true> : &gsr::k_render<true, false>);
+    // one wave per workgroup, four workgroups per tile (gsr_forward.hip)
+    hipLaunchKernelGGL(render_k, dim3(4 * f.tiles), dim3(64), 0, f.stream, f.ds, f.b.tile_order, f.b.qstart, f.b.qcount, f.g.grec, f.b.qpos, f.b.qlist,
+                       f.im.final_T, f.im.n_contrib, f.im.n_contrib_q, f.im.c_final, f.im.ck, out_color, f.cap, f.b.total, f.im.units, f.tiles);
+    KERNEL_CHECK("k_render", f.stream, f.dbg);
+    return 0;
+}
+
+// the blocking form: wait for the scan's post (early in the frame, not for the frame)
+static int await_count(const Frame& f, int64_t binning_capacity, int64_t* num_rendered_host)
+{
     unsigned long long v;
-    unsigned spins = 0;
-    for (;;) {
-        v = __atomic_load_n((unsigned long long*)slot, __ATOMIC_ACQUIRE);
-        if (v != 0 && (v >> 40) == seq) break;
-        if (++spins > 2000) {
-            std::this_thread::yield();
-            if ((spins & 0xFFF) == 0) {
-                if (hipStreamQuery(stream) != hipErrorNotReady) {
-                    // stream drained (or faulted) without a post
-                    v = __atomic_load_n((unsigned long long*)slot, __ATOMIC_ACQUIRE);
-                    if (v != 0 && (v >> 40) == seq) break;
-                    hipError_t e = hipStreamSynchronize(stream);
-                    return fail(GSR_E_HIP, "stream finished without posting the instance count: %s", hipGetErrorString(e));
-                }
-                if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(120))
-                    return fail(GSR_E_TIMEOUT, "timed out waiting for the instance count");
-            }
-        }
-    }
-    g_wait_ns.fetch_add((long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count());
-    g_waits.fetch_add(1);
+    if (int rc = await_post(f.slot, f.seq, f.stream, &v)) return rc;
     const int64_t I = (int64_t)(v & kCountMask);
     note_posted(GSR_COUNT_SLOTS, v);
     *num_rendered_host = I;
@@ -768,6 +709,46 @@ static int forward_impl(const GsrSettings* settings, int32_t P, int32_t M, const
     if (I > binning_capacity) return fail(GSR_E_CAPACITY, "binning capacity %lld < %lld instances", (long long)binning_capacity, (long long)I);
     return GSR_OK;
 }
+
+static int forward_impl(const GsrSettings* settings, int32_t P, int32_t M, const float* means3D, const float* shs, const float* shs_rest,
+                        const float* colors_precomp, const float* opacities, const float* scales, const float* rotations,
+                        const float* cov3D_precomp, float* out_color, int32_t* radii, void* geom, void* binning,
+                        int64_t binning_capacity, void* img, int64_t* num_rendered_host, void* stream_, const GsrBound* bound)
+{
+    gsr::PreprocessArgs pa;
+    pa.P = P; pa.M = M;
+    pa.means3D = means3D; pa.shs = shs; pa.shs_rest = shs_rest; pa.colors_precomp = colors_precomp; pa.opacities = opacities;
+    pa.scales = scales; pa.rotations = rotations; pa.cov3D_precomp = cov3D_precomp;
+    pa.radii = radii;
+    if (int rc = check_forward_args(settings, pa, out_color, geom, binning, binning_capacity, img, num_rendered_host)) return rc;
+
+    Frame f;
+    make_views(P, settings->image_width, settings->image_height, binning_capacity, settings->tile_culling, geom, binning, img, &f);
+    // the rank path addresses the four quadrant streams of a tile as 32-bit ELEMENT offsets 4 * start + q * n into qpos
+    if (f.bl.path != 1 && binning_capacity > (1ll << 30))
+        return fail(GSR_E_ARG, "binning_capacity %lld exceeds 2^30 tile instances (32-bit quadrant-stream offsets on this binning path)", (long long)binning_capacity);
+    if (int rc = g_mail.init()) return rc;
+    f.stream = (hipStream_t)stream_;
+    f.dbg = settings->debug != 0;
+    f.P = P; f.pblocks = (int)splat_blocks((size_t)P); f.tiles = (int)f.tg.tiles;
+    f.ds = to_dev_settings(settings);
+    f.ds.fast_blend = fast_effective(settings) ? 1 : 0;
+    f.cap = (unsigned long long)binning_capacity;
+
+    if (int rc = enqueue_preprocess(f, settings, pa, bound)) return rc;
+    if (int rc = open_post(f, settings)) return rc;
+    // Optimistic launch: the rest of the frame is enqueued against the caller's capacity before the
+    // host knows I; every kernel re-checks *total_dev <= capacity on the device and does nothing
+    // otherwise.  The host then waits only for the scan (early in the frame), not for the frame.
+    if (int rc = f.bl.path == 1 ? enqueue_scatter_binning(f) : enqueue_rank_binning(f)) return rc;
+    if (int rc = enqueue_render(f, out_color)) return rc;
+    if (settings->deferred_count != 0) {   // the count of this frame is not known yet: the caller checks its slot after the fact
+        *num_rendered_host = -1;
+        return GSR_OK;
+    }
+    return await_count(f, binning_capacity, num_rendered_host);
+}
+
 
 int gsr_forward_ex(const GsrSettings* settings, int32_t P, int32_t M, const float* means3D, const float* shs, const float* shs_rest,
                    const float* colors_precomp, const float* opacities, const float* scales, const float* rotations,
@@ -819,26 +800,22 @@ static int backward_impl(const GsrSettings* settings, int32_t P, int32_t M, cons
         return fail(GSR_E_ARG, "scales/rotations and their gradients required when cov3D is not precomputed");
 
     const int W = settings->image_width, H = settings->image_height;
-    const int gx = (W + GSR_BLOCK_X - 1) / GSR_BLOCK_X, gy = (H + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y;
     const bool dbg = settings->debug != 0;
-    GsrGeomLayout gl;
-    GsrBinningLayout bl;
-    GsrImageLayout il;
-    gsr_geom_layout(P, &gl);
-    gsr_binning_layout(binning_capacity, W, H, P, settings->tile_culling, &bl);
-    gsr_image_layout(W, H, &il);
-    char* g = (char*)geom;
-    const char* b = (const char*)binning;
-    const char* im = (const char*)img;
+    // the forward's views; of the binning and image states the backward only reads, but for the scratch word gmax
+    StateViews views;
+    make_views(P, W, H, binning_capacity, settings->tile_culling, geom, const_cast<void*>(binning), const_cast<void*>(img), &views);
+    const GeomView& g = views.g;
+    const BinView& b = views.b;
+    const ImageView& im = views.im;
+    const int tiles = (int)views.tg.tiles;
     gsr::Settings ds = to_dev_settings(settings);
     ds.fast_blend = fast_effective(settings) ? 1 : 0;
-    float* grad_scratch = (float*)(g + gl.acc);   // zeroed by the forward (and by the previous backward)
-    long long* acc64 = (long long*)(g + gl.acc64);
-    uint32_t* gmax = (uint32_t*)(const_cast<char*>(im) + il.gmax);   // scratch word of the image state
+    float* grad_scratch = g.acc_sums();   // zeroed by the forward (and by the previous backward)
+    long long* acc64 = g.acc64_sums();
     const bool det = settings->deterministic != 0;
     if (det) {   // the fixed-point scale of this backward: max |dL/dpixel|
-        HIP_TRY(hipMemsetAsync(gmax, 0, 4, stream));
-        hipLaunchKernelGGL(gsr::k_gmax, dim3(256), dim3(256), 0, stream, (size_t)3 * W * H, dL_dpix, gmax);
+        HIP_TRY(hipMemsetAsync(im.gmax, 0, 4, stream));
+        hipLaunchKernelGGL(gsr::k_gmax, dim3(256), dim3(256), 0, stream, (size_t)3 * W * H, dL_dpix, im.gmax);
         KERNEL_CHECK("k_gmax", stream, dbg);
     }
     if (num_rendered > 0) {
@@ -846,36 +823,31 @@ static int backward_impl(const GsrSettings* settings, int32_t P, int32_t M, cons
         if (ds.fast_blend) {   // fast blend: the record-parallel kernel
             // a fixed number of waves: every wave takes the units of its list in turn (gsr.h: GsrImageLayout.units), so the size only sets how many
             // share the work -- about one unit per wave at 100 k splats and 802 x 550, never more waves than four per (tile, segment)
-            int rp_grid = gx * gy * GSR_BWD_SEGMENTS;
+            int rp_grid = tiles * GSR_BWD_SEGMENTS;
             rp_grid = rp_grid < 3072 ? (rp_grid + 15) / 16 * 16 : 3072;   // a multiple of GSR_UNIT_LISTS / 4: every list sees the same stride
             // ONE wave per workgroup (round 6): a wave gets about one unit and units differ in cost by the half-rows that reach them (1 .. 16); in a
             // workgroup of four the slot of a finished wave stays taken until the slowest of the four is done
-            hipLaunchKernelGGL(gsr::k_render_bwd_rp, dim3(rp_grid * 4), dim3(64), 0, stream, ds,
-                               (const uint32_t*)(b + bl.qstart), (const uint32_t*)(b + bl.qcount), (const float4*)(g + gl.grec), (const uint32_t*)(b + bl.qpos),
-                               (const float*)(im + il.final_T), (const uint32_t*)(im + il.n_contrib_q), dL_dpix, grad_scratch,
-                               (const float*)(im + il.c_final), (const float4*)(im + il.ck), gx * gy,
-                               (unsigned long long)binning_capacity, (const unsigned long long*)b, (const uint32_t*)(im + il.units));
+            hipLaunchKernelGGL(gsr::k_render_bwd_rp, dim3(rp_grid * 4), dim3(64), 0, stream, ds, b.qstart, b.qcount, g.grec, b.qpos, im.final_T,
+                               im.n_contrib_q, dL_dpix, grad_scratch, im.c_final, im.ck, tiles, (unsigned long long)binning_capacity, b.total, im.units);
         } else {   // exact blend: the pixel-parallel walk, with fixed-point sums in the deterministic mode
             auto* const render_bwd = det ? &gsr::k_render_bwd<true> : &gsr::k_render_bwd<false>;
-            hipLaunchKernelGGL(render_bwd, dim3(gx * gy * GSR_BWD_SEGMENTS), dim3(256), 0, stream, ds, (const uint32_t*)(b + bl.tile_order),
-                               (const uint32_t*)(b + bl.qstart), (const uint32_t*)(b + bl.qcount), (const float4*)(g + gl.grec), (const uint32_t*)(b + bl.qpos),
-                               (const float*)(im + il.final_T), (const uint32_t*)(im + il.n_contrib_q), dL_dpix, grad_scratch,
-                               (const float*)(im + il.c_final), (const float4*)(im + il.ck), gx * gy, acc64, (const uint32_t*)gmax,
-                               (unsigned long long)binning_capacity, (const unsigned long long*)b);
+            hipLaunchKernelGGL(render_bwd, dim3(tiles * GSR_BWD_SEGMENTS), dim3(256), 0, stream, ds, b.tile_order, b.qstart, b.qcount, g.grec, b.qpos,
+                               im.final_T, im.n_contrib_q, dL_dpix, grad_scratch, im.c_final, im.ck, tiles, acc64, im.gmax,
+                               (unsigned long long)binning_capacity, b.total);
         }
         KERNEL_CHECK("k_render_bwd", stream, dbg);
     }
     gsr::PreBwdArgs pa;
     pa.P = P; pa.M = M;
     pa.means3D = means3D; pa.shs = shs; pa.shs_rest = shs_rest; pa.scales = scales; pa.rotations = rotations;
-    pa.cov3D = (const float*)(g + gl.cov3D);
+    pa.cov3D = g.cov3D;
     pa.radii = radii;
-    pa.clamped = (const uint8_t*)(g + gl.clamped);
+    pa.clamped = g.clamped;
     pa.acc = grad_scratch;
     pa.acc64 = acc64;
-    pa.gmax = gmax;
-    pa.grec = (const float4*)(g + gl.grec);
-    pa.shjac = gsr::sh_jac_stashed(false, pre_col, M) ? (const float*)(g + gl.shjac) : nullptr;   // (the forward of this state was not forward_only: checked above)
+    pa.gmax = im.gmax;
+    pa.grec = g.grec;
+    pa.shjac = gsr::sh_jac_stashed(false, pre_col, M) ? g.shjac : nullptr;   // (the forward of this state was not forward_only: checked above)
     pa.use_precomp_cov = pre_cov ? 1 : 0;
     pa.use_precomp_color = pre_col ? 1 : 0;
     pa.dL_dmeans3D = dL_dmeans3D; pa.dL_dmeans2D = dL_dmeans2D; pa.dL_dsh = pre_col ? nullptr : dL_dsh; pa.dL_dsh_rest = shs_rest ? dL_dsh_rest : nullptr;
@@ -893,6 +865,7 @@ static int backward_impl(const GsrSettings* settings, int32_t P, int32_t M, cons
     }
     return GSR_OK;
 }
+
 
 int gsr_backward_ex(const GsrSettings* settings, int32_t P, int32_t M, const float* means3D, const float* shs, const float* shs_rest,
                     const float* colors_precomp, const float* scales, const float* rotations, const float* cov3D_precomp,
@@ -962,6 +935,10 @@ int gsr_wait_stats(double* total_wait_ms, int64_t* waits)
     return GSR_OK;
 }
 
+// The ids and names are the profile's columns (bench.py keys on them) and predate the kernels they bracket today (TIMED above):
+// k_count: k_rcount; k_depth_sort: k_dbucket + k_dscan + k_dscatter + k_dsort, or k_rdscatter with its tile scan (bands: + k_rdsort, k_band_*);
+// k_scatter: k_rsort_rscatter or k_rscatter; k_tile_sort: k_tile_rank; k_qscan: k_qscan + k_qscan_glob; k_render_bwd: k_render_bwd or
+// k_render_bwd_rp; k_tile_scan: nothing since the per-tile sort went; the others one kernel of their own name.
 const char* gsr_kernel_name(int id)
 {
     static const char* names[GSR_NUM_KERNELS] = {"k_preprocess", "k_tile_scan", "k_scatter", "k_tile_sort",

@@ -488,7 +488,7 @@ struct BinHeader {              // first bytes of the binning buffer (include/gs
     uint32_t dmin_inv;              // production: ~(bits of the smallest binned depth)  (so that a zeroed slot is +inf)
     uint32_t dmax_bits;             // production: bits of the largest binned depth
     uint32_t dmin_bits;             // = ~dmin_inv
-    unsigned long long binned_tiles;// production: tile instances after snug-rect culling (what the per-tile sort path would bin)
+    unsigned long long binned_tiles;// production: tile instances after snug-rect culling (what the rank path would bin)
     uint32_t band_total[GSR_RANK_MAX_BANDS];   // rank path with bands: binned splats whose rect touches band b (= the band's rank space)
     uint32_t chunk_imbalance;       // rank path: 1 when the busiest 256 consecutive splats hold more than GSR_RANK_IMBALANCE x the mean's tile instances (k_rcount; posted with the count)
     uint32_t pad[21];

@@ -142,7 +142,7 @@ def _backward_may_follow(needs) -> bool:
 
 
 # ---- per-device running estimate of the binning capacity (instances per frame) -----------------
-# The capacity counts what the binning path produces: tile instances on the per-tile sort path, quadrant-stream entries on the production
+# The capacity counts what the binning path produces: tile instances on the rank path, quadrant-stream entries on the production
 # path (include/gsr.h: gsr_binning_layout) -- one running estimate per path, keyed (device index, H, W, production path?).
 _CAP_QUANTUM = 1 << 16
 _capacity_hint: dict = {}
@@ -565,7 +565,7 @@ def _launch_frame(lib, s, dev, P, bound, call, on_error) -> _Frame:
     else:
         I = cap      # unknown until the kernels have run
     _last_info.update(num_rendered=I if waited else -1, capacity=cap, replays=replays, tile_culling=bool(s.tile_culling), production_binning=prod, forward_only=bool(s.forward_only),
-                      binning_path=int(bl.path), rank_bands=int(bl.nbands), bound=bound)   # 0 rank path, 1 depth-ordered scatter, 2 per-tile sort (include/gsr.h)
+                      binning_path=int(bl.path), rank_bands=int(bl.nbands), bound=bound)   # 0 rank path, 1 depth-ordered scatter (include/gsr.h)
     _last_binning[0] = binning
     return _Frame(color, radii, geom[gl.visible: gl.visible + P].view(torch.bool), geom, binning, img, cap, I)
 

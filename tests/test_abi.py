@@ -50,12 +50,12 @@ def test_layouts_are_disjoint_and_aligned():
     rank_segs = [(bl.qpos, 16 * cap), (bl.qcount, 16 * tiles), (bl.qstart, 16 * tiles),
                  (bl.ranges, 8 * tiles), (bl.tile_count, 4 * tiles), (bl.tile_start, 4 * tiles), (bl.tile_cursor, 4 * tiles), (bl.tile_order, 4 * tiles),
                  (bl.block_hist, 4 * 256 * tiles), (bl.dkeys, 8 * P), (bl.dtmp, 8 * P), (bl.bcount, 4 * bl.nb), (bl.bstart, 4 * bl.nb),
-                 (bl.bcursor, 4 * bl.nb), (bl.bhist, 4 * 256 * bl.nb), (bl.ranks, 8 * cap), (bl.rank, 4 * P), (bl.srect, 8 * P), (bl.sspan, 32 * P), (bl.pstat, 8 * nblk), (bl.tdesc, 16 * tiles)]
+                 (bl.bcursor, 4 * bl.nb), (bl.bhist, 4 * 256 * bl.nb), (bl.ranks, 8 * cap), (bl.rank, 4 * P), (bl.srect, 8 * P), (bl.sspan, 32 * P), (bl.pstat, 80 * nblk + (256 + 4) * 4), (bl.tdesc, 16 * tiles)]
     _check(rank_segs + [(bl.keys, 8 * cap), (bl.point_list, 4 * cap), (bl.qlist, 16 * cap)], bl.total)
     # production settings up to 262144 splats: the same path without the reference-format lists
     assert lib.gsr_binning_layout(cap, 550, 802, P, 3, C.byref(bl)) == 0 and bl.path == 0
     assert bl.keys == bl.point_list and bl.qlist == bl.qpos
-    _check([(bl.qpos, 16 * cap), (bl.ranks, 8 * cap), (bl.point_list, 4 * cap), (bl.rank, 4 * P), (bl.srect, 8 * P), (bl.pstat, 8 * nblk)], bl.total)
+    _check([(bl.qpos, 16 * cap), (bl.ranks, 8 * cap), (bl.point_list, 4 * cap), (bl.rank, 4 * P), (bl.srect, 8 * P), (bl.pstat, 80 * nblk + (256 + 4) * 4)], bl.total)
     # tile_culling 5 selected the per-tile bitonic sort: removed, and an error rather than another path under the old number
     assert lib.gsr_binning_layout(cap, 550, 802, P, 5, C.byref(bl)) != 0 and b"per-tile sort was removed" in lib.gsr_last_error()
     # production: depth-ordered scatter into the quadrant streams (capacity counts stream entries)
@@ -84,6 +84,37 @@ def test_layouts_are_disjoint_and_aligned():
     assert lib.gsr_binning_layout(capq, 1600, 1100, 2_000_000, 5, C.byref(bl)) != 0 and b"per-tile sort was removed" in lib.gsr_last_error()
     _check([(il.final_T, 4 * HW), (il.n_contrib, 4 * HW), (il.n_contrib_q, 4 * HW), (il.c_final, 12 * HW), (il.ck, 144 * HW)], il.total)
     assert lib.gsr_geom_layout(-1, C.byref(gl)) < 0 and b"bad arguments" in lib.gsr_last_error()
+
+
+def test_layouts_are_the_recorded_bytes():
+    """The three layout functions return, byte for byte, what the library returned before its launch code was restructured around typed
+    views of the state buffers: the SHA-256 over the return codes and the raw GsrGeomLayout / GsrBinningLayout / GsrImageLayout
+    of 1200 combinations of image size, splat count, binning mode and capacity, recorded from the library of the commit before that change."""
+    import hashlib
+    import struct
+
+    from gaussianavatars_amd import _lib
+
+    lib = _lib.gsr()
+    h = hashlib.sha256()
+    n = 0
+    for W, H in ((17, 9), (550, 802), (802, 550), (1600, 1100), (2048, 2048)):
+        for P in (0, 1, 255, 256, 257, 100_000, 262_144, 262_145, 300_000, 2_000_000):
+            for mode in (0, 1, 2, 3, 4, 6):
+                for cap in (0, 65536, 3_000_000, 1 << 30):
+                    gl, bl, il = _lib.GsrGeomLayout(), _lib.GsrBinningLayout(), _lib.GsrImageLayout()
+                    rcs = (lib.gsr_geom_layout(P, C.byref(gl)), lib.gsr_binning_layout(cap, W, H, P, mode, C.byref(bl)),
+                           lib.gsr_image_layout(W, H, C.byref(il)))
+                    assert rcs == (0, 0, 0)
+                    h.update(struct.pack("<3i", *rcs) + bytes(gl) + bytes(bl) + bytes(il))
+                    n += 1
+    assert n == 1200
+    assert h.hexdigest() == "faa4d54bc562fac71dc37d73276f0c84f4e53ebb50348980dda8d1acba45dba3"
+    bl = _lib.GsrBinningLayout()
+    assert lib.gsr_binning_layout(65536, 550, 802, 100_000, 5, C.byref(bl)) == -1   # GSR_E_ARG
+    assert lib.gsr_last_error() == b"tile_culling 5: the per-tile sort was removed (binning modes are 0..4 and 6)"
+    assert lib.gsr_binning_layout(65536, 550, 802, 100_000, 7, C.byref(bl)) == -1   # GSR_E_ARG
+    assert lib.gsr_last_error() == b"tile_culling 7: binning modes are 0..4 and 6"
 
 
 @pytest.mark.parametrize("width,height", [(802, 550), (17, 9)])
