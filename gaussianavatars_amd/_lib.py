@@ -627,3 +627,43 @@ def gfs():
 gfs_error = partial(last_error, "gfs")
 gfs_profile_enable = partial(profile_enable, ("gfs",))
 gfs_profile_read = partial(profile_read, ("gfs",))
+
+
+# ------------------------------------------------------------------------------------------------
+# libgms_hip.so : the fused metric-space regularisers (include/gms.h).  Loaded only by loss.metric_regularizers, at the first call on device
+# tensors.
+# ------------------------------------------------------------------------------------------------
+#: tag -> LibSpec of the libraries added after FRAME_LIBS was pinned to ["gfs"] in its turn (tests/test_frames_cpu.py); the fifth table works
+#: exactly like the other four: handle(), last_error() and the profile shims take its tags, and build() checks all five
+REG_LIBS = {}
+
+GMS_LIB_PATH = _lib_path("gms")
+GMS_ABI_VERSION = 1
+GMS_SLAB = 1024               # include/gms.h: splats per workgroup
+GMS_MAX_SPLATS = 1 << 24      # include/gms.h: P must stay below this (the count is an exact float)
+GMS_ROW_BYTES = 8             # include/gms.h: bytes per splat of the backward's parked face contributions
+
+GMS_SYMBOLS = {
+    "gms_abi_version": (C.c_int, []),
+    "gms_last_error": (C.c_char_p, []),
+    "gms_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "gms_forward": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P, C.c_float, C.c_float, _P, _P, _P]),
+    "gms_backward": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P, C.c_float, C.c_float] + [_P] * 10),
+    **_profile_symbols("gms"),
+}
+
+REG_LIBS["gms"] = LibSpec("gms", GMS_LIB_PATH, GMS_SYMBOLS, GMS_ABI_VERSION)
+_gms = None
+
+
+def gms():
+    """The metric-space regulariser library; raises (never falls back) when it is not built."""
+    global _gms
+    if _gms is None:
+        _gms = _load(REG_LIBS["gms"])
+    return _gms
+
+
+gms_error = partial(last_error, "gms")
+gms_profile_enable = partial(profile_enable, ("gms",))
+gms_profile_read = partial(profile_read, ("gms",))

@@ -8,6 +8,8 @@ step should call).  There is no torch fallback: a CPU tensor or a missing librar
 `regularization_losses(gaussians, visibility_filter, opt)` is the drop-in for the two splat regularisers of a mesh-bound run
 (train.py:135-146) on the fused kernels of include/grl.h; `splat_regularizers` is the pair of means behind it.  Inputs outside those
 kernels' domain evaluate the reference's own composed expressions (they are the definition; a missing library still raises).
+`metric_regularizers` is the same pair in the metric forms of --metric_xyz / --metric_scale (train.py:136, :143) on the kernels of
+include/gms.h, with the gradient into face_scaling.
 """
 from __future__ import annotations
 
@@ -393,17 +395,17 @@ def _composed_regularizers(xyz, log_scaling, visibility_filter, threshold_xyz, t
 _REG_SCRATCH = {}   # (device index, raw stream) -> zeroed-once scratch of include/grl.h; never shared between two streams
 
 
-def _reg_scratch(dev, stream, nbytes):
+def _reg_scratch(dev, stream, nbytes, table=_REG_SCRATCH):
     """The (device, stream)'s scratch, grown when a larger model arrives.  The kernel leaves it ready for the next call on the same stream, so
     it is zeroed only here.  Under stream capture nothing is cached: a scratch made there lives in that graph's private pool, and its
-    zero-fill is recorded with it."""
+    zero-fill is recorded with it.  `table`: the library's own cache (include/grl.h and include/gms.h lay their scratch out differently)."""
     key = (dev.index, stream)
-    held = _REG_SCRATCH.get(key)
+    held = table.get(key)
     if held is not None and held.numel() >= nbytes:
         return held
     held = torch.zeros(max(nbytes, 4096), dtype=torch.uint8, device=dev)
     if not torch.cuda.is_current_stream_capturing():
-        _REG_SCRATCH[key] = held
+        table[key] = held
     return held
 
 
@@ -470,15 +472,159 @@ def splat_regularizers(xyz: torch.Tensor, log_scaling: torch.Tensor, visibility_
     return _SplatRegularizers.apply(xyz.contiguous(), log_scaling.contiguous(), visibility_filter.contiguous(), float(threshold_xyz), float(threshold_scale))
 
 
+# ---- the metric forms of the same two terms (train.py:136, :143) on the fused kernels of include/gms.h ----------------------------------------
+def _composed_metric_regularizers(xyz, log_scaling, face_scaling, binding, visibility_filter, threshold_xyz, threshold_scale, want_xyz=True, want_scale=True):
+    """train.py:136 and :143 as the reference writes them, without their lambdas; get_scaling spelled out
+    (scene/gaussian_model.py:113-118: exp(_scaling) * face_scaling[binding])."""
+    F = torch.nn.functional
+    fs = face_scaling if face_scaling.dim() == 2 else face_scaling[:, None]
+    xyz_mean = F.relu((xyz * fs[binding])[visibility_filter] - threshold_xyz).norm(dim=1).mean() if want_xyz else None
+    scale_mean = F.relu((torch.exp(log_scaling) * fs[binding])[visibility_filter] - threshold_scale).norm(dim=1).mean() if want_scale else None
+    return xyz_mean, scale_mean
+
+
+_METRIC_SCRATCH = {}   # (device index, raw stream) -> zeroed-once scratch of include/gms.h; never shared between two streams
+_METRIC_CSR = {}       # device index -> (key, the binding tensor, its CSR): the last binding seen there, for callers that hold no CSR of their own
+
+
+def _metric_csr(binding, num_faces):
+    """binding.binding_csr of `binding`, kept per device and keyed on the tensor's storage pointer, in-place version and shape (and the face
+    count): rebuilt only after a densification replaced or rewrote the binding.  The entry keeps the tensor alive, so its address cannot be
+    handed to another tensor while the key stands.  Under stream capture nothing is cached (_reg_scratch's rule)."""
+    from . import binding as _binding
+
+    key = (binding.data_ptr(), binding._version, tuple(binding.shape), tuple(binding.stride()), binding.dtype, int(num_faces))
+    held = _METRIC_CSR.get(binding.device.index)
+    if held is not None and held[0] == key:
+        return held[2]
+    csr = _binding.binding_csr(binding, int(num_faces))
+    if not torch.cuda.is_current_stream_capturing():
+        _METRIC_CSR[binding.device.index] = (key, binding, csr)
+    return csr
+
+
+def _metric_launch(dev, what, fn, *args):
+    with _lib.on_device(dev):
+        rc = fn(*args)
+    if rc != 0:
+        raise RuntimeError(f"{what} failed ({rc}): {_lib.gms_error()}")
+
+
+class _MetricRegularizers(torch.autograd.Function):
+    """(P,3) x (P,3) x (F,) x (P,) int x (P,) bool -> (xyz_mean, scale_mean): one launch forward; one launch backward for the per-splat
+    gradients, which recomputes from the inputs, and one more that sums each face's run of the binding's CSR when face_scaling wants its
+    gradient (include/gms.h).  The two scalars are views of the node's 4-float result made inside forward, like _SplatRegularizers'."""
+
+    @staticmethod
+    def forward(ctx, xyz, log_scaling, face_scaling, binding, visible, threshold_xyz, threshold_scale, want_xyz, want_scale, csr):
+        ctx.set_materialize_grads(False)
+        lib = _lib.gms()
+        dev = xyz.device
+        P, F = xyz.shape[0], face_scaling.shape[0]
+        stream = _stream(dev)
+        out = torch.empty(4, dtype=torch.float32, device=dev)
+        scratch = _reg_scratch(dev, stream, int(lib.gms_scratch_bytes(P, F)), _METRIC_SCRATCH)
+        ctx.is64 = int(binding.dtype is torch.int64)
+        _metric_launch(dev, "gms_forward", lib.gms_forward, P, F, _p(xyz) if want_xyz else None, _p(log_scaling) if want_scale else None, _p(face_scaling),
+                       _p(binding), ctx.is64, _p(visible), threshold_xyz, threshold_scale, _p(out), _p(scratch), stream)
+        ctx.save_for_backward(xyz, log_scaling, face_scaling, binding, visible)
+        ctx.out, ctx.thresholds, ctx.want, ctx.csr = out, (threshold_xyz, threshold_scale), (want_xyz, want_scale), csr
+        return out[0], out[1]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_xyz, g_scale):
+        xyz, log_scaling, face_scaling, binding, visible = ctx.saved_tensors
+        on_x = ctx.want[0] and g_xyz is not None          # the term is on: selected in the forward and reached by the loss
+        on_s = ctx.want[1] and g_scale is not None
+        need_x = ctx.needs_input_grad[0] and on_x
+        need_s = ctx.needs_input_grad[1] and on_s
+        need_f = ctx.needs_input_grad[2] and (on_x or on_s)
+        if not (need_x or need_s or need_f):
+            return (None,) * 10
+        if need_f and ctx.csr is None:
+            raise RuntimeError("metric_regularizers: the gradient into face_scaling needs the binding's CSR (binding.binding_csr)")
+        lib = _lib.gms()
+        dev = xyz.device
+        P, F = xyz.shape[0], face_scaling.shape[0]
+        gx = g_xyz.to(torch.float32).contiguous() if on_x else None
+        gs = g_scale.to(torch.float32).contiguous() if on_s else None
+        d_xyz = torch.empty_like(xyz) if need_x else None
+        d_ls = torch.empty_like(log_scaling) if need_s else None
+        d_face = face_begin = slot = rows = None
+        if need_f:
+            d_face = torch.empty_like(face_scaling)
+            face_begin, slot = ctx.csr[1], ctx.csr[3]
+            rows = torch.empty(max(P, 1), dtype=torch.float64, device=dev)   # (GMS_ROW_BYTES per splat)
+        _metric_launch(dev, "gms_backward", lib.gms_backward, P, F, _p(xyz) if on_x else None, _p(log_scaling) if on_s else None, _p(face_scaling), _p(binding),
+                       ctx.is64, _p(visible), ctx.thresholds[0], ctx.thresholds[1], _p(ctx.out), _p(gx), _p(gs), _p(d_xyz), _p(d_ls), _p(d_face),
+                       _p(face_begin), _p(slot), _p(rows), _stream(dev))
+        return (d_xyz, d_ls, d_face) + (None,) * 7
+
+
+def metric_regularizers(xyz: torch.Tensor, log_scaling: torch.Tensor, face_scaling: torch.Tensor, binding: torch.Tensor, visibility_filter: torch.Tensor,
+                        threshold_xyz: float, threshold_scale: float, want_xyz: bool = True, want_scale: bool = True, csr=None):
+    """-> (xyz_mean, scale_mean), the two means of train.py:136 and :143 before their lambdas (a term that is not wanted is None and costs nothing):
+
+        xyz_mean   = relu((xyz * face_scaling[binding])[visibility_filter] - threshold_xyz).norm(dim=1).mean()
+        scale_mean = relu((exp(log_scaling) * face_scaling[binding])[visibility_filter] - threshold_scale).norm(dim=1).mean()
+
+    from ONE launch, with gradients for xyz, log_scaling and face_scaling: one launch in the backward for the two per-splat gradients and a
+    second, a fixed-order sum over each face's splats, when face_scaling requires a gradient -- no mask gather, no host wait, no float atomics
+    (include/gms.h).  That second launch walks the binding's per-face CSR: `csr` = binding.binding_csr(binding, F) when the caller holds one
+    (a model's binding backward does), else it is built here and kept until the binding tensor changes; it is not needed, and not built,
+    when face_scaling requires no gradient.
+    The kernels take float32 (P,3) device tensors, a float32 face_scaling of shape (F,1) or (F,), an int32 or int64 binding (P,), a bool (P,)
+    filter, all on the same device, and P < 2^24; non-contiguous inputs are made contiguous.  Anything else -- CPU tensors, another dtype, an
+    index list as the filter -- evaluates the two expressions above in composed torch and returns the same tuple.  No visible splat gives NaN
+    (the mean of an empty tensor) and zero gradients."""
+    if not (want_xyz or want_scale):
+        return None, None
+    tensors = (xyz, log_scaling, face_scaling, binding, visibility_filter)
+    ok = (all(isinstance(t, torch.Tensor) and t.is_cuda and t.device == xyz.device for t in tensors)
+          and xyz.dtype is torch.float32 and log_scaling.dtype is torch.float32 and face_scaling.dtype is torch.float32
+          and visibility_filter.dtype is torch.bool and binding.dtype in (torch.int32, torch.int64)
+          and xyz.dim() == 2 and xyz.shape[1] == 3 and log_scaling.shape == xyz.shape and visibility_filter.shape == (xyz.shape[0],)
+          and binding.shape == (xyz.shape[0],) and (face_scaling.dim() == 1 or (face_scaling.dim() == 2 and face_scaling.shape[1] == 1))
+          and face_scaling.shape[0] >= 1 and xyz.shape[0] < _lib.GMS_MAX_SPLATS)
+    if not ok:
+        return _composed_metric_regularizers(xyz, log_scaling, face_scaling, binding, visibility_filter, threshold_xyz, threshold_scale, want_xyz, want_scale)
+    P, F = xyz.shape[0], face_scaling.shape[0]
+    if face_scaling.requires_grad and torch.is_grad_enabled():
+        if csr is None:
+            csr = _metric_csr(binding, F)   # (keyed on the caller's tensor: the contiguous copy of a strided binding is a new tensor every call)
+        elif len(csr) < 4 or csr[1].numel() != F + 1 or csr[3].numel() != P:
+            raise RuntimeError(f"binding CSR does not match this call: expected {P} splats / {F} faces (rebuild it with binding_csr after the binding changed)")
+    else:
+        csr = None
+    binding = binding.detach().contiguous()
+    xm, sm = _MetricRegularizers.apply(xyz.contiguous(), log_scaling.contiguous(), face_scaling.contiguous(), binding, visibility_filter.contiguous(),
+                                       float(threshold_xyz), float(threshold_scale), bool(want_xyz), bool(want_scale), csr)
+    return (xm if want_xyz else None), (sm if want_scale else None)
+
+
+def _model_csr(gaussians, num_faces):
+    """The binding CSR a model already holds for its binding backward (patch.binding_csr_cached keeps it on the model and rebuilds it when the
+    binding changes); None for an object that cannot carry one, and metric_regularizers then keeps its own."""
+    from . import patch as _patch
+
+    try:
+        return _patch.binding_csr_cached(gaussians, num_faces)
+    except AttributeError:   # (an object with __slots__)
+        return None
+
+
 def regularization_losses(gaussians, visibility_filter, opt) -> dict:
     """The drop-in for train.py:135-146: `losses.update(regularization_losses(gaussians, visibility_filter, opt))`.
 
     -> {'xyz': ...} plus 'scale' when opt.lambda_scale != 0, each already multiplied by its lambda; {} for an unbound model
     (gaussians.binding is None: the `if` of train.py:134).  With opt.metric_xyz and opt.metric_scale both false -- the defaults of
-    arguments/__init__.py -- both terms come from one fused call of splat_regularizers.  A metric flag sends ITS term to the reference's
-    composed-torch line: the metric forms multiply by face_scaling[binding] and so send gradient into the face frames, which needs a per-face
-    reduction that is deliberately not part of the fused kernels.  GAA_FUSED_REG=0 forces composed torch for both terms.  The loop's other
-    regularisers (dy_off, lap, dynamic_offset_std: zero weight by default) stay the script's own lines."""
+    arguments/__init__.py -- both terms come from one fused call of splat_regularizers.  A metric flag takes ITS term from
+    metric_regularizers: the metric forms multiply by face_scaling[binding] and so send gradient into the face frames, through a per-face
+    reduction over the binding's CSR (the one the model holds for its binding backward).  The metric scale term reads _scaling, face_scaling
+    and binding itself instead of get_scaling, so the binding op is not launched a second time.  One metric and one local flag make one
+    call of each, each with the other term off.  GAA_FUSED_REG=0 forces composed torch for both terms.  The loop's other regularisers
+    (dy_off, lap, dynamic_offset_std: zero weight by default) stay the script's own lines."""
     if gaussians.binding is None:
         return {}
     F = torch.nn.functional
@@ -486,11 +632,23 @@ def regularization_losses(gaussians, visibility_filter, opt) -> dict:
     fused = os.environ.get("GAA_FUSED_REG", "1") != "0"
     fuse_xyz = fused and not opt.metric_xyz
     fuse_scale = fused and want_scale and not opt.metric_scale
+    metric_xyz = fused and bool(opt.metric_xyz)
+    metric_scale = fused and want_scale and bool(opt.metric_scale)
     losses = {}
     xyz_mean = scale_mean = None
     if fuse_xyz or fuse_scale:   # one call; a term that is not taken from it gets no upstream gradient and costs the backward nothing
         fx, fs = splat_regularizers(gaussians._xyz, gaussians._scaling, visibility_filter, opt.threshold_xyz, opt.threshold_scale)
         xyz_mean, scale_mean = (fx if fuse_xyz else None), (fs if fuse_scale else None)
+    if metric_xyz or metric_scale:   # one call; a term that is off is neither read nor computed
+        if gaussians.face_scaling is None and metric_scale and hasattr(gaussians, "select_mesh_by_timestep"):
+            gaussians.select_mesh_by_timestep(0)   # (get_scaling's lazy first mesh update: scene/gaussian_model.py:115-116)
+        face_scaling = gaussians.face_scaling
+        csr = None
+        if isinstance(face_scaling, torch.Tensor) and face_scaling.is_cuda and face_scaling.requires_grad and torch.is_grad_enabled():
+            csr = _model_csr(gaussians, face_scaling.shape[0])
+        mx, ms = metric_regularizers(gaussians._xyz, gaussians._scaling, face_scaling, gaussians.binding, visibility_filter, opt.threshold_xyz,
+                                     opt.threshold_scale, want_xyz=metric_xyz, want_scale=metric_scale, csr=csr)
+        xyz_mean, scale_mean = (mx if metric_xyz else xyz_mean), (ms if metric_scale else scale_mean)
     if xyz_mean is None:
         if opt.metric_xyz:
             xyz_mean = F.relu((gaussians._xyz * gaussians.face_scaling[gaussians.binding])[visibility_filter] - opt.threshold_xyz).norm(dim=1).mean()
