@@ -667,3 +667,54 @@ def gms():
 gms_error = partial(last_error, "gms")
 gms_profile_enable = partial(profile_enable, ("gms",))
 gms_profile_read = partial(profile_read, ("gms",))
+
+
+# ------------------------------------------------------------------------------------------------
+# libglp_hip.so : LPIPS for evaluation (include/glp.h).  Loaded only by lpips.py, at the first call on device tensors.
+# ------------------------------------------------------------------------------------------------
+#: tag -> LibSpec of the libraries added after REG_LIBS was pinned to ["gms"] in its turn (tests/test_metric_reg_cpu.py); the sixth table works
+#: exactly like the other five: handle(), last_error() and the profile shims take its tags, and build() checks all six
+LPIPS_LIBS = {}
+
+GLP_LIB_PATH = _lib_path("glp")
+GLP_ABI_VERSION = 1
+GLP_NET_ALEX, GLP_NET_VGG = 0, 1   # include/glp.h: the two backbones
+GLP_TAPS = 5                       # include/glp.h: taps of either net
+GLP_MAX_CONVS = 13                 # include/glp.h: convolutions of the larger net
+GLP_TILE = 64                      # include/glp.h: output channels per workgroup of glp_conv2d (Cout is a multiple)
+GLP_KBLOCK = 16                    # include/glp.h: packed weights are zero-padded to a multiple of this many reduction rows
+GLP_HEAD_BLOCKS = 256              # include/glp.h: most partials of one glp_head launch
+GLP_OUT_FLOATS = 6                 # include/glp.h: five per-tap terms and their sum
+
+GLP_SYMBOLS = {
+    "glp_abi_version": (C.c_int, []),
+    "glp_last_error": (C.c_char_p, []),
+    "glp_net_convs": (C.c_int, [C.c_int32]),
+    "glp_packed_floats": (C.c_int64, [C.c_int32] * 3),
+    "glp_pack_weights": (C.c_int, [C.c_int32] * 3 + [_P, _P, _P]),
+    "glp_conv2d": (C.c_int, [C.c_int32] * 8 + [_P, _P, _P, C.c_int32, _P, _P]),
+    "glp_maxpool": (C.c_int, [C.c_int64] + [C.c_int32] * 4 + [_P, _P, _P]),
+    "glp_zscore": (C.c_int, [C.c_int32] * 3 + [_P, _P, _P, _P]),
+    "glp_head_blocks": (C.c_int32, [C.c_int32] * 3),
+    "glp_head": (C.c_int, [C.c_int32] * 4 + [_P, _P, _P, _P]),
+    "glp_finish": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P]),
+    "glp_workspace_bytes": (C.c_int64, [C.c_int32] * 4),
+    "glp_forward": (C.c_int, [C.c_int32] * 4 + [_P, _P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _P, _P, _P]),
+    **_profile_symbols("glp"),
+}
+
+LPIPS_LIBS["glp"] = LibSpec("glp", GLP_LIB_PATH, GLP_SYMBOLS, GLP_ABI_VERSION)
+_glp = None
+
+
+def glp():
+    """The LPIPS library; raises (never falls back) when it is not built."""
+    global _glp
+    if _glp is None:
+        _glp = _load(LPIPS_LIBS["glp"])
+    return _glp
+
+
+glp_error = partial(last_error, "glp")
+glp_profile_enable = partial(profile_enable, ("glp",))
+glp_profile_read = partial(profile_read, ("glp",))

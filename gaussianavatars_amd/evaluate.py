@@ -5,8 +5,12 @@
     to_u8(image, also=None)         the bytes render.py:41 writes, interleaved, on the device (one launch, optionally for a second image)
     MetricAccumulator               running L1 / PSNR / SSIM of N views that stay on the device: update() launches and never waits,
                                     result() is the one host read
-    evaluate_views(...)             the loop of train.py:274-303 without tensorboard and LPIPS
+    evaluate_views(...)             the loop of train.py:274-303 without tensorboard
     score_directories / evaluate    metrics.py's scoring of the written PNGs, `python -m gaussianavatars_amd.evaluate -m MODEL_PATH ...`
+
+LPIPS (lpips.py, include/glp.h) joins each of the last three when its weights are configured -- lpips.weights_available(): `alex` in
+evaluate_views (train.py:296), `vgg` in the metrics.py paths (metrics.py:74) -- and only then: without weights every result is exactly what it
+was, with no "LPIPS" key anywhere.
 
 An image of a pair is fp32 planar, (C,H,W) or (B,C,H,W), or uint8 interleaved, (H,W,C) or (B,H,W,C) -- what a decoded PNG is, read as
 byte / 255.  `transform` applies to the fp32 ones: "raw", "clamp" (train.py:277-278) or "png8" (the byte to_u8 would write, / 255: the image
@@ -241,13 +245,22 @@ def to_u8(image, also=None):
 class MetricAccumulator:
     """Running L1 / PSNR / SSIM of up to `n_views` images, resident on `device`: a (n_views, 3) fp32 table of the per-view figures and four
     doubles [l1, psnr, ssim, count].  The sums are fp64 sums of fp32 figures, as the reference's `.double()` followed by `+=` makes them
-    (train.py:286-288).  `update` enqueues two launches and returns; `result` reads the 32 bytes."""
+    (train.py:286-288).  `update` enqueues two launches and returns; `result` reads the 32 bytes.
+    `lpips_net` ("alex" / "vgg"): when that net's weights are configured (lpips.weights_available), every view's LPIPS over the same transformed
+    pair is kept in a table of its own and `result` gains "lpips", their mean (one more read); otherwise nothing changes."""
 
-    def __init__(self, n_views: int, device):
+    def __init__(self, n_views: int, device, lpips_net=None):
         self.device = torch.device(device)
         self.table = torch.zeros((int(n_views), 3), dtype=torch.float32, device=self.device)
         self.acc = torch.zeros(4, dtype=torch.float64, device=self.device)
         self.n = 0   # rows handed out (host-side: known without reading the device)
+        self.lpips_net = self.lpips_table = None
+        if lpips_net is not None:
+            from . import lpips as L
+
+            if L.weights_available(lpips_net):
+                self.lpips_net = lpips_net
+                self.lpips_table = torch.zeros(int(n_views), dtype=torch.float32, device=self.device)
 
     def update(self, image, gt, transform="clamp", per_channel_psnr=None) -> None:
         per_channel = _per_channel(image, per_channel_psnr)
@@ -262,23 +275,37 @@ class MetricAccumulator:
             self.table[self.n:self.n + B] = rows
             self.acc[:3] += rows.double().sum(0)
             self.acc[3] += B
+        if self.lpips_net is not None:
+            from . import lpips as L
+
+            with torch.no_grad():   # one image at a time: the reference's sum over a batch (train.py:296) is the sum of these
+                a, b = _planar(image, transform), _planar(gt, transform)
+                for i in range(B):
+                    self.lpips_table[self.n + i] = L.lpips(a[i:i + 1], b[i:i + 1].to(a), self.lpips_net).reshape(()).to(self.device)
         self.n += B
 
     def result(self) -> dict:
-        """dict(l1, psnr, ssim, n): the means over the views so far (Python floats), after one host read."""
+        """dict(l1, psnr, ssim, n): the means over the views so far (Python floats), after one host read; with LPIPS on, also `lpips`."""
         l1, ps, ss, n = self.acc.tolist()
+        more = {} if self.lpips_net is None else dict(lpips=float(self.lpips_table[:self.n].double().mean()) if self.n else float("nan"))
         if n == 0:
-            return dict(l1=float("nan"), psnr=float("nan"), ssim=float("nan"), n=0)
-        return dict(l1=l1 / n, psnr=ps / n, ssim=ss / n, n=int(n))
+            return dict(l1=float("nan"), psnr=float("nan"), ssim=float("nan"), n=0, **more)
+        return dict(l1=l1 / n, psnr=ps / n, ssim=ss / n, n=int(n), **more)
 
     def per_view(self):
         """(n, 3) fp32 device tensor: [l1, psnr, ssim] of every view so far, in the order of the updates."""
         return self.table[:self.n]
 
+    def per_view_lpips(self):
+        """(n,) fp32 device tensor: the LPIPS of every view so far, or None when LPIPS is off."""
+        return None if self.lpips_net is None else self.lpips_table[:self.n]
+
 
 def evaluate_views(gaussians, views, pipe, bg, render=None):
-    """The loop body of train.py:274-303 over `views`, without tensorboard and LPIPS: select the mesh by the view's timestep when the model has
-    more than one, render, clamp both images and accumulate.  -> (l1, psnr, ssim) means as Python floats.  One host read, at the end."""
+    """The loop body of train.py:274-303 over `views`, without tensorboard: select the mesh by the view's timestep when the model has
+    more than one, render, clamp both images and accumulate.  -> (l1, psnr, ssim) means as Python floats.  One host read, at the end.
+    With the `alex` LPIPS weights configured (lpips.weights_available("alex"); train.py:296's net) -> (l1, psnr, ssim, lpips): the mean over
+    the views of their LPIPS, which is what train.py:302 forms from its sums over batches of 16."""
     if render is None:
         from .gaussian_renderer import render
     views = list(views)
@@ -289,12 +316,12 @@ def evaluate_views(gaussians, views, pipe, bg, render=None):
                 gaussians.select_mesh_by_timestep(view.timestep)
             image = render(view, gaussians, pipe, bg)["render"]
             if acc is None:
-                acc = MetricAccumulator(len(views), image.device)
+                acc = MetricAccumulator(len(views), image.device, lpips_net="alex")
             acc.update(image, view.original_image.to(image.device), transform="clamp")
     if acc is None:
         raise ValueError("no views to evaluate")
     r = acc.result()
-    return r["l1"], r["psnr"], r["ssim"]
+    return (r["l1"], r["psnr"], r["ssim"]) + ((r["lpips"],) if "lpips" in r else ())
 
 
 def _decode(path):
@@ -314,22 +341,27 @@ def score_directories(renders_dir, gt_dir, device=None):
     """metrics.py:62-86 for one method: SSIM and PSNR of every file of `renders_dir` against the file of the same name in `gt_dir`.  PIL decodes
     on the host, the bytes are uploaded as they are (uint8 interleaved; the kernels divide by 255 as to_tensor does), and the running sums stay
     on the device.  -> (full, per_view) with the reference's key layout: {"SSIM": mean, "PSNR": mean} and {"SSIM": {name: value}, "PSNR": {...}}.
-    There is no "LPIPS" key: its VGG weights and torchvision are not available to this package, and a made-up value would be worse than none."""
+    "LPIPS" (net `vgg`, metrics.py:74) joins both dicts when, and only when, its weights are configured (lpips.weights_available("vgg")): a
+    made-up value would be worse than none."""
     dev = torch.device(device) if device is not None else torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     names = sorted(os.listdir(renders_dir))
-    acc = MetricAccumulator(max(len(names), 1), dev)
+    acc = MetricAccumulator(max(len(names), 1), dev, lpips_net="vgg")
     for name in names:
         a, b = _decode(os.path.join(renders_dir, name)), _decode(os.path.join(gt_dir, name))
         acc.update(a[None].to(dev), b[None].to(dev), transform="raw", per_channel_psnr=False)
     r, rows = acc.result(), acc.per_view().tolist()
     full = {"SSIM": r["ssim"], "PSNR": r["psnr"]}
     per_view = {"SSIM": {n: row[2] for n, row in zip(names, rows)}, "PSNR": {n: row[1] for n, row in zip(names, rows)}}
+    if "lpips" in r:
+        full["LPIPS"] = r["lpips"]
+        per_view["LPIPS"] = dict(zip(names, acc.per_view_lpips().tolist()))
     return full, per_view
 
 
 def evaluate(model_paths, device=None) -> dict:
-    """metrics.py:36-93 without LPIPS: for every model path, every method under <path>/test is scored (its `renders` against its `gt`) and
-    <path>/results.json and <path>/per_view.json are written.  -> {model path: {method: {"SSIM": ..., "PSNR": ...}}}."""
+    """metrics.py:36-93: for every model path, every method under <path>/test is scored (its `renders` against its `gt`) and
+    <path>/results.json and <path>/per_view.json are written.  -> {model path: {method: {"SSIM": ..., "PSNR": ...}}}, with "LPIPS" beside them
+    when the `vgg` weights are configured."""
     out = {}
     for scene_dir in model_paths:
         print("Scene:", scene_dir)
@@ -341,6 +373,8 @@ def evaluate(model_paths, device=None) -> dict:
             print("Method:", method)
             print("  SSIM : {:>12.7f}".format(full[method]["SSIM"]))
             print("  PSNR : {:>12.7f}".format(full[method]["PSNR"]))
+            if "LPIPS" in full[method]:
+                print("  LPIPS: {:>12.7f}".format(full[method]["LPIPS"]))
         with open(os.path.join(scene_dir, "results.json"), "w") as fp:
             json.dump(full, fp, indent=True)
         with open(os.path.join(scene_dir, "per_view.json"), "w") as fp:
@@ -352,7 +386,8 @@ def evaluate(model_paths, device=None) -> dict:
 def main(argv=None) -> None:
     from argparse import ArgumentParser
 
-    parser = ArgumentParser(description="SSIM and PSNR of the rendered test views of trained models (metrics.py without LPIPS)")
+    parser = ArgumentParser(description="SSIM and PSNR of the rendered test views of trained models (metrics.py), and LPIPS when GAA_LPIPS_DIR "
+                                        "holds vgg16.pth and vgg.pth")
     parser.add_argument("--model_paths", "-m", required=True, nargs="+", type=str, default=[])
     evaluate(parser.parse_args(argv).model_paths)
 

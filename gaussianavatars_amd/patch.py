@@ -309,7 +309,7 @@ def unpatch_classes(*classes) -> None:
             del _ORIG[(cls, name)]
     for cls in classes:
         for flag in ("_gaa_patched", "_gaa_patched_flame", "_gaa_patched_head", "_gaa_patched_base", "_gaa_patched_stats", "_gaa_patched_optimizer",
-                     "_gaa_patched_overlay", "_gaa_patched_eval", "_gaa_orig_psnr", "_gaa_patched_frames"):
+                     "_gaa_patched_overlay", "_gaa_patched_eval", "_gaa_orig_psnr", "_gaa_patched_frames", "_gaa_patched_lpips"):
             if flag in cls.__dict__:
                 delattr(cls, flag)
         if isinstance(cls.__dict__.get("get_features_split"), property) and cls.__dict__["get_features_split"].fget is _get_features_split:
@@ -340,8 +340,12 @@ def patch_reference(reference_root: str | None = None, fast_render: bool = True,
     10. (GAA_FRAME_STORE=0 opts out) adopt_frame_store: `scene.Scene.getTrainCameras` returns a frames.ResidentCameraDataset: the ground truth and
        the cameras of the training frames stay in HBM (include/gfs.h), train.py:55's DataLoader workers pass placeholders on and train.py:128's
        `.cuda()` is one launch instead of a 5.3 MB pageable upload.
+    11. (GAA_FUSED_LPIPS=0 opts out) adopt_lpips: with LPIPS weights configured (lpips.weights_available: load_weights or GAA_LPIPS_DIR),
+       `lpipsPyTorch.lpips` (train.py:26,296, metrics.py:18,74) -> lpips.lpips on the kernels of include/glp.h, so the evaluation pass needs
+       neither torchvision nor a download; without weights nothing is touched.
     Returns {'shims': [...], 'classes': [...], 'render': bool, 'pinned_cpus': [...] | None, 'backward_seed': bool, 'loss': [...],
-    'optimizer': [...], 'overlay': [...], 'evaluation': [...], 'frames': [...]}.  Call it before the entry script imports `render`."""
+    'optimizer': [...], 'overlay': [...], 'evaluation': [...], 'frames': [...], 'lpips': [...]}.  Call it before the entry script imports
+    `render`."""
     from . import shims
 
     repo_root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -381,8 +385,9 @@ def patch_reference(reference_root: str | None = None, fast_render: bool = True,
     overlay = adopt_mesh_overlay() if os.environ.get("GAA_FUSED_OVERLAY", "1") != "0" else []
     evaluation = adopt_evaluation() if os.environ.get("GAA_FUSED_EVAL", "1") != "0" else []
     frames = adopt_frame_store() if os.environ.get("GAA_FRAME_STORE", "1") != "0" else []
+    fused_lpips = adopt_lpips() if os.environ.get("GAA_FUSED_LPIPS", "1") != "0" else []
     return dict(shims=served, classes=[gm.GaussianModel, fgm.FlameGaussianModel, flame.FlameHead], render=did_render, pinned_cpus=pinned,
-                backward_seed=seeded, loss=fused_loss, optimizer=fused_adam, overlay=overlay, evaluation=evaluation, frames=frames)
+                backward_seed=seeded, loss=fused_loss, optimizer=fused_adam, overlay=overlay, evaluation=evaluation, frames=frames, lpips=fused_lpips)
 
 
 def _make_resident_getter(orig, name, device):
@@ -434,6 +439,32 @@ def adopt_frame_store(scene_cls=None, device=None) -> list:
         done.append(f"{cls.__name__}.{name}")
     cls._gaa_patched_frames = True
     return done
+
+
+def adopt_lpips(module=None) -> list:
+    """LPIPS behind the zero-edit boundary: when weights of either net are configured (lpips.weights_available) and GAA_FUSED_LPIPS is not 0,
+    rebinds `lpipsPyTorch.lpips` (or that of `module`, any module with an `lpips`) to lpips.lpips BEFORE train.py:26 / metrics.py:18 bind it --
+    the same signature and (1,1,1,1) result, on the kernels of include/glp.h for device fp32 images.  A net whose weights are not configured
+    raises, naming the files it wants.  Without weights, or without an importable `lpipsPyTorch`, nothing is touched.  Idempotent; undone by
+    unpatch_classes(module).  Returns the names rebound."""
+    from . import lpips as L
+
+    if not L.fused_default() or not (L.weights_available("alex") or L.weights_available("vgg")):
+        return []
+    mod = module
+    if mod is None:
+        import importlib
+
+        try:
+            mod = importlib.import_module("lpipsPyTorch")
+        except ImportError:
+            return []
+    if getattr(mod, "_gaa_patched_lpips", False) or not hasattr(mod, "lpips"):
+        return []
+    _ORIG[(mod, "lpips")] = mod.lpips
+    mod.lpips = L.lpips
+    mod._gaa_patched_lpips = True
+    return [f"{getattr(mod, '__name__', 'lpipsPyTorch')}.lpips"]
 
 
 def adopt_evaluation(image_utils=None) -> list:
