@@ -333,35 +333,67 @@ template __global__ void k_render_bwd<true>(Settings, const uint32_t*, const uin
 //
 // The walk above gives every lane a pixel and every record a turn: 64 pixels x (73 VALU + 19 scalar instructions) per record, a
 // third of them the 64-lane reduction of the nine per-splat sums.  Here the roles are swapped: a wave still owns (quadrant, 60-entry
-// segment of its stream), but its LANES hold the segment's 60 records (one 48-byte gather per lane and segment, highest entry in lane
-// 0: back to front in lane order), and the quadrant's pixels take turns, four at a time (half a pixel row).  What was a serial
-// recurrence over the records becomes two wave scans per pixel,
-//     T_k   = T_end * prod_{i<=k} 1/(1 - alpha_i)               (transmittance in front of record k: prefix product over lanes)
+// segment of its stream), but its LANES hold the segment's 60 records, and the quadrant's pixels take turns, four at a time.  What was
+// a serial recurrence over the records becomes two scans per pixel,
+//     T_k   = T_end * prod_{i<=k} 1/(1 - alpha_i)               (transmittance in front of record k: prefix product over records)
 //     S_k   = S_end + sum_{i<k} alpha_i T_i (c_i . dL/dC)       (what lies behind record k, dotted with the pixel's gradient)
 // started from the forward's checkpoint at the segment's upper end exactly as the pixel-parallel kernel starts its walk; what was a
-// 64-lane reduction per record disappears -- every lane keeps the nine sums of ITS record in registers and adds them to the splat's
-// accumulator once per segment.  Per-pixel operands are wave-uniform (one LDS table per wave, broadcast reads); two pixels share every
-// arithmetic instruction through packed fp32 (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32), the scans of four pixels are issued
-// interleaved so that the DPP read-after-write distance is covered by useful instructions.
-// tests/test_fast_blend_gpu.py holds it to the oracle; it is the fast blend's only backward.
+// 64-lane reduction per record disappears -- every lane keeps the nine sums of ITS records in registers and adds them to the splats'
+// accumulators once per segment.
+// Lane mapping: a lane holds TWO consecutive records -- lane l of a half-wave entries hi-1-2l (the "even" record,
+// farther back) and hi-2-2l (the "odd" one), lanes 30 and 31 of each half idle -- as the two halves of packed fp32 operands
+// (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32: one instruction per term covers two records of one pixel).  The two half-waves hold the SAME
+// 60 records and work on different pixels of the same row: lanes 0..31 on columns 0..3, lanes 32..63 on columns 4..7; a "slot" s = 0..3
+// is one register across the wave = columns s and s + 4, a step is two slots = four pixels.  A scan then runs over 32 lanes in both
+// halves at once: the lane's two values are folded first, five DPP steps scan the folds, and the even record's value is taken back out
+// of the inclusive one (14 instructions per slot for both scans; one record per lane took 24 per two pixels).  Per-pixel operands come
+// from one LDS table per wave, read per half (broadcast within the half).
+// tests/test_fast_blend_gpu.py and tests/test_render_bwd_pairs_gpu.py hold it to the oracle; it is the fast blend's only backward.
 // ------------------------------------------------------------------------------------------
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 
-// inclusive prefix scans over the 64 lanes of FOUR registers at once (in place).  v_OP_dpp dst, dst, dst: dst = shifted(dst) OP dst where
+// inclusive prefix scans over each 32-lane half of TWO registers at once (in place).  v_OP_dpp dst, dst, dst: dst = shifted(dst) OP dst where
 // the shift has a source lane, unchanged elsewhere (bound_ctrl off disables the write) -- one instruction per step and register, which
 // the compiler will not form from the builtin for a multiply (its "old" operand has to be the identity, re-materialised per step).
-// A DPP operand needs two wait states behind the VALU write of the same register: the four chains provide three.
-#define GSR_SCAN4_STEP(OP, CTRL)                                      \
-    OP " %0, %0, %0 " CTRL "\n\t" OP " %1, %1, %1 " CTRL "\n\t" OP " %2, %2, %2 " CTRL "\n\t" OP " %3, %3, %3 " CTRL "\n\t"
-#define GSR_SCAN4(OP, a, b, c, d)                                                                      \
-    asm volatile("s_nop 1\n\t" GSR_SCAN4_STEP(OP, "row_shr:1 row_mask:0xf bank_mask:0xf")              \
-                 GSR_SCAN4_STEP(OP, "row_shr:2 row_mask:0xf bank_mask:0xf")                            \
-                 GSR_SCAN4_STEP(OP, "row_shr:4 row_mask:0xf bank_mask:0xf")                            \
-                 GSR_SCAN4_STEP(OP, "row_shr:8 row_mask:0xf bank_mask:0xf")                            \
-                 GSR_SCAN4_STEP(OP, "row_bcast:15 row_mask:0xa bank_mask:0xf")                         \
-                 GSR_SCAN4_STEP(OP, "row_bcast:31 row_mask:0xc bank_mask:0xf")                         \
-                 : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
+// row_bcast:15 with row_mask 0xa carries lane 15 of rows 0 and 2 into rows 1 and 3: each half is complete after it, and nothing crosses
+// from lanes 0..31 into 32..63.  A DPP operand needs two wait states behind the VALU write of the same register: the other chain is one,
+// and the second is a packed operation of the step that does not depend on the scan -- six per scan, written here because the compiler
+// cannot schedule into an asm block (left outside they cost an s_nop per step, and the splat of a pair's HIGH half a v_mov each):
+//   product scan: the two slots' c . dL/dC = cr g0 + (cgn g1 + cb g2); a slot's g come as the pairs (g0, g1) and (g2, last) of its table entry
+//   sum scan:     the two slots' colour sums a0 += alpha T g0, a1 += alpha T g1, a2 += alpha T g2
+// (op_sel / op_sel_hi pick the half of a source pair that feeds the low / high result: [0,.] [0,.] splats the low half, [1,.] [1,.] the high one)
+#define GSR_DPP2(OP, A, B, CTRL) OP " " A ", " A ", " A " " CTRL "\n\t" OP " " B ", " B ", " B " " CTRL "\n\t"
+#define GSR_SPLAT_LO " op_sel:[0,0,0] op_sel_hi:[1,0,1]\n\t"
+#define GSR_SPLAT_HI " op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+#define GSR_SCAN2_MUL_CG(Ra, Rb, cg0, cg1, cr, cgn, cb, gA0, gB0, gA1, gB1)                                         \
+    asm volatile("s_nop 1\n\t" GSR_DPP2("v_mul_f32_dpp", "%0", "%1", "row_shr:1 row_mask:0xf bank_mask:0xf")        \
+                 "v_pk_mul_f32 %2, %6, %8 op_sel:[0,0] op_sel_hi:[1,0]\n\t"                                         \
+                 GSR_DPP2("v_mul_f32_dpp", "%0", "%1", "row_shr:2 row_mask:0xf bank_mask:0xf")                       \
+                 "v_pk_mul_f32 %3, %6, %10 op_sel:[0,0] op_sel_hi:[1,0]\n\t"                                        \
+                 GSR_DPP2("v_mul_f32_dpp", "%0", "%1", "row_shr:4 row_mask:0xf bank_mask:0xf")                       \
+                 "v_pk_fma_f32 %2, %5, %7, %2" GSR_SPLAT_HI                                                         \
+                 GSR_DPP2("v_mul_f32_dpp", "%0", "%1", "row_shr:8 row_mask:0xf bank_mask:0xf")                       \
+                 "v_pk_fma_f32 %3, %5, %9, %3" GSR_SPLAT_HI                                                         \
+                 GSR_DPP2("v_mul_f32_dpp", "%0", "%1", "row_bcast:15 row_mask:0xa bank_mask:0xf")                    \
+                 "v_pk_fma_f32 %2, %4, %7, %2" GSR_SPLAT_LO                                                         \
+                 "v_pk_fma_f32 %3, %4, %9, %3" GSR_SPLAT_LO                                                         \
+                 : "+v"(Ra), "+v"(Rb), "=&v"(cg0), "=&v"(cg1)                                                       \
+                 : "v"(cr), "v"(cgn), "v"(cb), "v"(gA0), "v"(gB0), "v"(gA1), "v"(gB1))
+#define GSR_SCAN2_ADD_COL(Wa, Wb, a0, a1, a2, aT0, aT1, gA0, gB0, gA1, gB1)                                         \
+    asm volatile("s_nop 1\n\t" GSR_DPP2("v_add_f32_dpp", "%0", "%1", "row_shr:1 row_mask:0xf bank_mask:0xf")        \
+                 "v_pk_fma_f32 %2, %5, %7, %2" GSR_SPLAT_LO                                                         \
+                 GSR_DPP2("v_add_f32_dpp", "%0", "%1", "row_shr:2 row_mask:0xf bank_mask:0xf")                       \
+                 "v_pk_fma_f32 %3, %5, %7, %3" GSR_SPLAT_HI                                                         \
+                 GSR_DPP2("v_add_f32_dpp", "%0", "%1", "row_shr:4 row_mask:0xf bank_mask:0xf")                       \
+                 "v_pk_fma_f32 %4, %5, %8, %4" GSR_SPLAT_LO                                                         \
+                 GSR_DPP2("v_add_f32_dpp", "%0", "%1", "row_shr:8 row_mask:0xf bank_mask:0xf")                       \
+                 "v_pk_fma_f32 %2, %6, %9, %2" GSR_SPLAT_LO                                                         \
+                 GSR_DPP2("v_add_f32_dpp", "%0", "%1", "row_bcast:15 row_mask:0xa bank_mask:0xf")                    \
+                 "v_pk_fma_f32 %3, %6, %9, %3" GSR_SPLAT_HI                                                         \
+                 "v_pk_fma_f32 %4, %6, %10, %4" GSR_SPLAT_LO                                                        \
+                 : "+v"(Wa), "+v"(Wb), "+v"(a0), "+v"(a1), "+v"(a2)                                                 \
+                 : "v"(aT0), "v"(aT1), "v"(gA0), "v"(gB0), "v"(gA1), "v"(gB1))
 
 __global__ __launch_bounds__(64) void k_render_bwd_rp(Settings s, const uint32_t* __restrict__ qstart,
                                                         const uint32_t* __restrict__ qcount, const float4* __restrict__ grec,
@@ -375,14 +407,17 @@ __global__ __launch_bounds__(64) void k_render_bwd_rp(Settings s, const uint32_t
     // ONE wave per workgroup (waves share nothing).  The wave's index is still read from threadIdx: written with the constant
     // folded, the compiler schedules the prologue differently, and this kernel's instruction stream is kept as it was measured.
     constexpr int WPB = 1;
-    __shared__ __attribute__((aligned(16))) float tab_all[WPB][32 * 12];   // the wave's pixel table (below)
-    __shared__ float xpose_all[WPB][64 * 9];                                // the nine sums of every lane on their way out
-    constexpr int CH = GSR_BWD_SEGMENT;          // records per chunk = lanes in use (60 of 64)
-    static_assert(CH <= 64 && CH > 32, "a chunk of the stream has to fit the wave");
+    __shared__ __attribute__((aligned(16))) float tab_all[WPB][64 * 8];    // the wave's pixel table (below)
+    __shared__ float xpose_all[WPB][64 * 9];                                // the nine sums of every record on their way out
+    __shared__ __attribute__((aligned(8))) uint32_t ids_all[WPB][64];       // the chunk's splat ids by record (entry hi - 1 - k at [k])
+    constexpr int CH = GSR_BWD_SEGMENT;          // records per chunk, two per lane (lanes 0..29 of each half-wave)
+    constexpr int HL = CH / 2;                   // lanes of a half-wave in use
+    static_assert(CH <= 64 && CH % 2 == 0, "a chunk of the stream has to fit a half-wave, two records per lane");
     const int W = s.W, H = s.H;
     const int gx = (W + GSR_BLOCK_X - 1) / GSR_BLOCK_X;
     const int wave_in_wg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
+    const int hl = lane & 31, hf = lane >> 5;    // lane of the half-wave; which half (columns 4 hf .. 4 hf + 3 of a row)
     // ---- the wave's UNITS (gsr.h: GsrImageLayout.units): entries p, p + stride, ... of list (wave id mod GSR_UNIT_LISTS); every unit is a
     // (tile, quadrant, segment) the forward found a contributor in, so a wave that gets one has work (round 3 launched a workgroup per (tile,
     // segment): four of five found nothing, and the waves of the others were tied to the four quadrants whether those reached the segment or not)
@@ -394,6 +429,8 @@ __global__ __launch_bounds__(64) void k_render_bwd_rp(Settings s, const uint32_t
     const uint32_t* __restrict__ ulist = units + 32u * GSR_UNIT_LISTS + list * ucap;
     float* const tab = tab_all[wave_in_wg];
     float* const xs = xpose_all[wave_in_wg];
+    uint32_t* const ids = ids_all[wave_in_wg];
+    const float* const tabh = tab + 8 * hf;      // this half-wave's entries of the table
     for (uint32_t up = wid / (uint32_t)GSR_UNIT_LISTS; up < ucount; up += ustride) {
     // (from the END of the list: the forward appends a quadrant's units when its walk is over, so the deep quadrants -- whose open-ended last segment
     //  is many chunks for one wave -- come last in the list; taken first they are not the kernel's tail: template-like frame 109.8 -> see DESIGN.md 7.6)
@@ -432,100 +469,105 @@ __global__ __launch_bounds__(64) void k_render_bwd_rp(Settings s, const uint32_t
                 Sx += (c_final[0 * HW + pix_id] - c.y) * g0 + (c_final[1 * HW + pix_id] - c.z) * g1 + (c_final[2 * HW + pix_id] - c.w) * g2;
             }
         }
-        // ---- the wave's pixel table (LDS, 12 floats per PAIR of horizontally adjacent pixels, three broadcast ds_read_b128 per pair):
-        //      (T_end, T_end', S, S' | g0, g0', g1, g1' | g2, g2', last, last')
-        float* tw = tab + ((lane >> 3) * 4 + ((lane & 7) >> 1)) * 12 + (lane & 1);
-        tw[0] = Tend; tw[2] = Sx; tw[4] = g0; tw[6] = g1; tw[8] = g2; tw[10] = __int_as_float(last_pix);
+        // ---- the wave's pixel table (LDS, 8 floats per pixel, six of them used: (T_end, S, g0, g1 | g2, last, -, -); the pixel of row r
+        //      and column c = s + 4 half sits at [(4 r + s) * 2 + half], so the entry a lane needs for slot s of row r is at one address per
+        //      half-wave: a ds_read_b128 and a ds_read_b64 per slot, broadcast within each half)
+        float* tw = tab + (((lane >> 3) * 4 + (lane & 3)) * 2 + ((lane >> 2) & 1)) * 8;
+        tw[0] = Tend; tw[1] = Sx; tw[2] = g0; tw[3] = g1; tw[4] = g2; tw[5] = __int_as_float(last_pix);
     }
-    const float fqx0 = (float)qx0, fqy0 = (float)qy0;
+    const float fqx0 = (float)(qx0 + 4 * hf), fqy0 = (float)qy0;   // (x relative to the first column of the lane's half)
 
     for (;;) {
         const int lo = hi - CH;
-        // ---- this lane's RECORD: entry hi - 1 - lane of the stream (lanes CH.. and entries past the end: opacity 0, never hit)
-        const int j = hi - 1 - lane;
-        const bool valid = lane < CH && j < nq;
-        const uint32_t idx = qp[valid ? j : nq - 1];
-        const float4 r0 = grec[3 * (size_t)idx + 0], r1 = grec[3 * (size_t)idx + 1], r2 = grec[3 * (size_t)idx + 2];
-        const float xq = r0.x - fqx0, yq = r0.y - fqy0;          // relative to the quadrant's first pixel
-        const float cA = r0.z, cB = r0.w, cC = r1.x;             // the conic, pre-scaled into the 2^x domain (k_preprocess)
-        const float op = valid ? r2.z : 0.f;                      // (fast-blend record: slot 5 holds log2(opacity) for the forward, slot 10 the opacity)
-        const float cr = r1.z, cgn = r1.w, cb = r2.x;
-        const int jrec = valid ? j : 0x7fffffff;                 // "last > jrec" is the pixel's range test
-        const unsigned long long act = __ballot(last_pix > lo);  // pixels with something in this chunk
+        // ---- this lane's two RECORDS: entries hi - 1 - 2 hl ("even", .x of every pair) and hi - 2 - 2 hl ("odd", .y) of the stream, the same
+        //      in both half-waves (lanes HL.. of a half and entries past the end: opacity 0, never hit -- a lane may hold one of each kind)
+        const int jE = hi - 1 - 2 * hl, jO = jE - 1;
+        const bool validE = hl < HL && jE < nq, validO = hl < HL && jO < nq;
+        const uint32_t idxE = qp[validE ? jE : nq - 1], idxO = qp[validO ? jO : nq - 1];
+        if (hf == 0) *reinterpret_cast<uint2*>(ids + 2 * hl) = make_uint2(idxE, idxO);
+        const float4 e0 = grec[3 * (size_t)idxE + 0], e1 = grec[3 * (size_t)idxE + 1], e2 = grec[3 * (size_t)idxE + 2];
+        const float4 o0 = grec[3 * (size_t)idxO + 0], o1 = grec[3 * (size_t)idxO + 1], o2 = grec[3 * (size_t)idxO + 2];
+        const f2 xq = {e0.x - fqx0, o0.x - fqx0}, yq = {e0.y - fqy0, o0.y - fqy0};   // relative to the first pixel of the quadrant's half
+        const f2 cA = {e0.z, o0.z}, cB = {e0.w, o0.w}, cC = {e1.x, o1.x};             // the conic, pre-scaled into the 2^x domain (k_preprocess)
+        const f2 op = {validE ? e2.z : 0.f, validO ? o2.z : 0.f};   // (fast-blend record: slot 5 holds log2(opacity) for the forward, slot 10 the opacity)
+        const f2 cr = {e1.z, o1.z}, cgn = {e1.w, o1.w}, cb = {e2.x, o2.x};
+        // "last > entry" is the pixel's range test: last > jrec for the even record, last >= jrec for the odd one, the entry below it.  (A lane
+        // whose odd record alone is valid: its even entry lies at or past the stream's end, where no pixel's `last` reaches.)
+        const int jrec = validO ? jE : 0x7fffffff;
+        const unsigned long long act = __ballot(last_pix > lo);  // pixels with something in this chunk (bit 8 row + column)
         const bool more = lo > seg_lo;                           // (open-ended segment) another chunk follows below this one
         f2 a0 = {0.f, 0.f}, a1 = a0, a2 = a0, a3 = a0, a4 = a0, a5 = a0, a6 = a0, a7 = a0, a8 = a0;
 
         for (int r = 0; r < 8; ++r) {
             const uint32_t rm = (uint32_t)(act >> (8 * r)) & 0xFFu;
             if (!rm) continue;
-            const float dy = yq - (float)r;
-            const float Bdy = cB * dy, Cdy2 = (cC * dy) * dy;
+            const f2 dy = yq - (float)r;
+            const f2 Bdy = cB * dy, Cdy2 = (cC * dy) * dy;
             // the six position moments of tq = G dL/dG: dy is the same for the row's eight pixels, so the row adds up (sum tq, sum tq dx, sum tq dx^2)
-            // and the three dy-weighted sums are formed once per row (4 packed operations per pixel pair instead of 8)
+            // and the three dy-weighted sums are formed once per row (4 packed operations per slot instead of 8)
             f2 rs0 = {0.f, 0.f}, rs1 = rs0, rs2 = rs0;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                if (!((rm >> (4 * h)) & 0xFu)) continue;
-                const f4* tp = reinterpret_cast<const f4*>(tab + (r * 4 + 2 * h) * 12);
-                f4 t[2][3];
-#pragma unroll
-                for (int e = 0; e < 2; ++e)
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) t[e][k] = tp[3 * e + k];
-                f2 dx[2], a0m[2], al[2], rv[2], R[2], Tj[2], cg[2], aT[2], Pw[2];
+                if (!((rm >> (2 * h)) & 0x33u)) continue;       // slots 2h, 2h + 1 = columns 2h, 2h + 1 (low half) and 2h + 4, 2h + 5 (high half)
+                const float* tp = tabh + (r * 4 + 2 * h) * 16;
+                f4 tA[2];
+                f2 tB[2];
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
-                    const float c0 = (float)(4 * h + 2 * e);
-                    dx[e] = f2{xq - c0, xq - (c0 + 1.0f)};
+                    tA[e] = *reinterpret_cast<const f4*>(tp + 16 * e);
+                    tB[e] = *reinterpret_cast<const f2*>(tp + 16 * e + 4);
+                }
+                f2 dx[2], a0m[2], al[2], rv[2], Tj[2], cg[2], aT[2], Pw[2], D[2];
+                float omO[2], R[2], Ws[2];
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    dx[e] = xq - (float)(2 * h + e);
                     const f2 pw = (cA * dx[e] + Bdy) * dx[e] + Cdy2;
                     const f2 G = {__builtin_amdgcn_exp2f(pw.x), __builtin_amdgcn_exp2f(pw.y)};
                     const f2 araw = op * G;
-                    const int l0 = __float_as_int(t[e][2].z), l1 = __float_as_int(t[e][2].w);
-                    a0m[e].x = (l0 > jrec && araw.x >= 1.0f / 255.0f) ? araw.x : 0.0f;
-                    a0m[e].y = (l1 > jrec && araw.y >= 1.0f / 255.0f) ? araw.y : 0.0f;
+                    const int l = __float_as_int(tB[e].y);
+                    a0m[e].x = (l > jrec && araw.x >= 1.0f / 255.0f) ? araw.x : 0.0f;
+                    a0m[e].y = (l >= jrec && araw.y >= 1.0f / 255.0f) ? araw.y : 0.0f;
                     al[e] = f2{__builtin_fminf(0.99f, a0m[e].x), __builtin_fminf(0.99f, a0m[e].y)};
                     const f2 om = 1.0f - al[e];
                     rv[e] = f2{__builtin_amdgcn_rcpf(om.x), __builtin_amdgcn_rcpf(om.y)};
-                    R[e] = rv[e];
+                    omO[e] = om.y;
+                    R[e] = rv[e].x * rv[e].y;       // the lane's two records as one factor of the scan
                 }
-                GSR_SCAN4("v_mul_f32_dpp", R[0].x, R[0].y, R[1].x, R[1].y);
+                const f2 gA0 = {tA[0].z, tA[0].w}, gA1 = {tA[1].z, tA[1].w};   // (g0, g1) of the two slots; tB is (g2, last)
+                GSR_SCAN2_MUL_CG(R[0], R[1], cg[0], cg[1], cr, cgn, cb, gA0, tB[0], gA1, tB[1]);
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
-                    const f2 Te = {t[e][0].x, t[e][0].y};
-                    const f2 g0 = {t[e][1].x, t[e][1].y}, g1 = {t[e][1].z, t[e][1].w}, g2 = {t[e][2].x, t[e][2].y};
-                    Tj[e] = Te * R[e];
-                    cg[e] = cr * g0 + (cgn * g1 + cb * g2);
+                    const float Te = tA[e].x;
+                    // the inclusive product is the odd record's (it is the nearer one); the even record's lacks the odd one's factor
+                    Tj[e] = Te * f2{R[e] * omO[e], R[e]};
                     aT[e] = al[e] * Tj[e];
-                    Pw[e] = aT[e] * cg[e];      // w = alpha T (c . dL/dC); scanned in place
+                    Pw[e] = aT[e] * cg[e];      // w = alpha T (c . dL/dC)
+                    Ws[e] = Pw[e].x + Pw[e].y;  // scanned in place
+                    D[e] = Tj[e] * cg[e] - tA[e].y;                     // T c.g - S_end: all the second scan's result still has to meet
                 }
-                GSR_SCAN4("v_add_f32_dpp", Pw[0].x, Pw[0].y, Pw[1].x, Pw[1].y);
+                // (open-ended segment) the chunk below starts from the state at this chunk's lower end: the odd record of lane HL-1 of each half
+                // is the lowest entry -- the transmittance in front of it here, the sum behind it after the second scan
+                if (more) {
+                    float* up = tab + ((r * 4 + 2 * h) * 2 + hf) * 8;
+                    if (hl == HL - 1) { up[0] = Tj[0].y; up[16] = Tj[1].y; }
+                }
+                GSR_SCAN2_ADD_COL(Ws[0], Ws[1], a0, a1, a2, aT[0], aT[1], gA0, tB[0], gA1, tB[1]);
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
-                    const f2 Sx = {t[e][0].z, t[e][0].w};
-                    const f2 g0 = {t[e][1].x, t[e][1].y}, g1 = {t[e][1].z, t[e][1].w}, g2 = {t[e][2].x, t[e][2].y};
+                    const f2 inc = {Ws[e] - Pw[e].y, Ws[e]};            // inclusive sums of the two records
                     // dL/dalpha = T c.g - S / (1 - alpha), S = what lies behind the record = (inclusive sum - w) + S_end; with w = alpha T c.g and
-                    // 1 + alpha / (1 - alpha) = 1 / (1 - alpha) that is (T c.g - inclusive sum - S_end) / (1 - alpha)
-                    const f2 dLda = ((Tj[e] * cg[e] - Pw[e]) - Sx) * rv[e];
+                    // 1 + alpha / (1 - alpha) = 1 / (1 - alpha) that is (T c.g - S_end - inclusive sum) / (1 - alpha)
+                    const f2 dLda = (D[e] - inc) * rv[e];
                     const f2 tq = a0m[e] * dLda;                        // opacity * G * dL/dalpha  (= G * dL/dG; the 0.99 clamp has no gradient)
-                    a0 += aT[e] * g0;
-                    a1 += aT[e] * g1;
-                    a2 += aT[e] * g2;
                     const f2 ax = tq * dx[e];
                     rs0 += tq;
                     rs1 += ax;
                     rs2 += ax * dx[e];
-                    if (more) {
-                        // state at the chunk's lower end for the chunk below: lane CH-1 holds the lowest entry -- the transmittance in front of it
-                        // and, inclusive of it, the sum behind
-                        const float T0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Tj[e].x), CH - 1));
-                        const float T1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Tj[e].y), CH - 1));
-                        const float S0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Pw[e].x), CH - 1)) + Sx.x;
-                        const float S1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Pw[e].y), CH - 1)) + Sx.y;
-                        if (lane == 0) {
-                            float* up = tab + (r * 4 + 2 * h + e) * 12;
-                            up[0] = T0; up[1] = T1; up[2] = S0; up[3] = S1;
-                        }
-                    }
+                }
+                if (more) {
+                    float* up = tab + ((r * 4 + 2 * h) * 2 + hf) * 8;
+                    if (hl == HL - 1) { up[1] += Ws[0]; up[17] += Ws[1]; }   // S_end + the chunk's inclusive sum
                 }
             }
             a3 += rs1;                                                  // k_preprocess_bwd forms A sx + B sy, C sy + B sx and the constant factors
@@ -539,18 +581,24 @@ __global__ __launch_bounds__(64) void k_render_bwd_rp(Settings s, const uint32_t
         // units (measured: the kernel three times slower than the walk it replaces); instead the sums cross the wave through LDS and leave
         // record-major -- lane e of pass i carries element 64 i + e of the (record, component) matrix, so each record's nine floats are
         // consecutive lanes of one instruction and reach its 48-byte accumulator as one burst.
+        // The two half-waves summed the same records over different pixels: one v_permlane32_swap per sum trades the high half of the even
+        // records' register for the low half of the odd records', after which one add leaves the even record's total in lane hl and the odd
+        // record's in lane 32 + hl -- record 2 hl + hf of the chunk (entry hi - 1 - record) in every lane.
         {
-            const float v[9] = {a0.x + a0.y, a1.x + a1.y, a2.x + a2.y, a3.x + a3.y, a4.x + a4.y, a5.x + a5.y, a6.x + a6.y, a7.x + a7.y, a8.x + a8.y};
+            const f2 a[9] = {a0, a1, a2, a3, a4, a5, a6, a7, a8};
 #pragma unroll
-            for (int c = 0; c < 9; ++c) xs[9 * lane + c] = v[c];
+            for (int c = 0; c < 9; ++c) {
+                const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(a[c].x), __float_as_uint(a[c].y), false, false);
+                xs[9 * (2 * hl + hf) + c] = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
+            }
             // seven records (63 lanes) per pass: a record's nine floats never straddle two instructions
 #pragma unroll
             for (int i = 0; i < (CH + 6) / 7; ++i) {
                 const int rl7 = (lane * 7282) >> 16;                             // lane / 9 (0..7)
                 const int c = lane - 9 * rl7;
-                const int rl = 7 * i + rl7;                                      // the lane whose record this is
+                const int rl = 7 * i + rl7;                                      // the record of the chunk this is
                 const float val = xs[63 * i + lane];
-                const uint32_t rid = (uint32_t)__builtin_amdgcn_ds_bpermute(rl << 2, (int)idx);   // its splat
+                const uint32_t rid = ids[rl];                                    // its splat
                 const bool live = lane < 63 && rl < CH && (hi - 1 - rl) < nq;
                 if (live && val != 0.f) unsafeAtomicAdd(acc + (size_t)GSR_ACC_STRIDE * rid + c, val);
             }
