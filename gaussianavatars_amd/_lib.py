@@ -80,7 +80,7 @@ def _torch_first():
 
 def _load(spec):
     """Map one library and check it against its description; raises (never falls back) when it is not built, lacks a symbol or is stale.
-    The caller keeps the handle: gsr() ... grl() below each cache theirs in a module global, so their warm path is a global load and a test."""
+    The caller keeps the handle: the loaders _register() returns each cache theirs."""
     if not os.path.exists(spec.path):
         raise RuntimeError(
             f"{spec.path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -96,6 +96,23 @@ def _load(spec):
     if have != spec.abi:
         raise RuntimeError(f"{spec.tag} ABI version {have} != {spec.abi}")
     return lib
+
+
+def _register(tag, symbols, abi, env=None):
+    """Enter lib<tag>_hip.so into LIBS and return its loader <tag>(): the first call maps and checks the file, later calls return the same
+    handle.  The handle is a cell of the closure, so the warm path is a cell load and a test."""
+    LIBS[tag] = LibSpec(tag, _lib_path(tag, env), symbols, abi)
+    lib = None
+
+    def loader():
+        nonlocal lib
+        if lib is None:
+            lib = _load(LIBS[tag])
+        return lib
+
+    loader.__name__ = loader.__qualname__ = tag
+    loader.__doc__ = f"lib{tag}_hip.so, mapped and checked at the first call; raises (never falls back) when it is not built."
+    return loader
 
 
 def _profile_symbols(tag):
@@ -142,8 +159,6 @@ def profile_read(tags) -> dict:
 # ------------------------------------------------------------------------------------------------
 # libgsr_hip.so : the splat rasterizer (include/gsr.h)
 # ------------------------------------------------------------------------------------------------
-GSR_LIB_PATH = _lib_path("gsr", "GSR_LIB")
-
 GSR_OK = 0
 GSR_ABI_VERSION = 12
 GSR_E_CAPACITY = 1
@@ -253,22 +268,13 @@ def gsr_wait_stats():
     return ms.value, n.value
 
 
-LIBS["gsr"] = LibSpec("gsr", GSR_LIB_PATH, GSR_SYMBOLS, GSR_ABI_VERSION)
-_gsr = None
-
-
-def gsr():
-    """The rasterizer library; raises (never falls back) when it is not built."""
-    global _gsr
-    if _gsr is None:
-        _gsr = _load(LIBS["gsr"])
-    return _gsr
+gsr = _register("gsr", GSR_SYMBOLS, GSR_ABI_VERSION, "GSR_LIB")
+GSR_LIB_PATH = LIBS["gsr"].path   # bench.py and _host.py read it
 
 
 # ------------------------------------------------------------------------------------------------
 # libgab_hip.so : FLAME / face-frame / splat binding kernels (include/gab.h)
 # ------------------------------------------------------------------------------------------------
-GAB_LIB_PATH = _lib_path("gab", "GAB_LIB")
 GAB_FLAME_WS_FLOATS = 512
 GAB_BIND_ROW_FLOATS = 20   # include/gab.h: floats per splat of the two-pass CSR backward's scratch
 _P = C.c_void_p
@@ -307,22 +313,13 @@ GAB_SYMBOLS = {
 }
 GAB_ABI_VERSION = 5
 
-LIBS["gab"] = LibSpec("gab", GAB_LIB_PATH, GAB_SYMBOLS, GAB_ABI_VERSION)
-_gab = None
-
-
-def gab():
-    """The binding library; raises (never falls back) when it is not built."""
-    global _gab
-    if _gab is None:
-        _gab = _load(LIBS["gab"])
-    return _gab
+gab = _register("gab", GAB_SYMBOLS, GAB_ABI_VERSION, "GAB_LIB")
+GAB_LIB_PATH = LIBS["gab"].path   # bench.py and _host.py read it
 
 
 # ------------------------------------------------------------------------------------------------
 # libgls_hip.so : fused L1 + SSIM loss and densification statistics (include/gls.h)
 # ------------------------------------------------------------------------------------------------
-GLS_LIB_PATH = _lib_path("gls")
 GLS_SYMBOLS = {
     "gls_abi_version": (C.c_int, []),
     "gls_last_error": (C.c_char_p, []),
@@ -339,31 +336,14 @@ GLS_SYMBOLS = {
 }
 GLS_ABI_VERSION = 4
 
-LIBS["gls"] = LibSpec("gls", GLS_LIB_PATH, GLS_SYMBOLS, GLS_ABI_VERSION)
-_gls = None
-
-
-def gls():
-    """The loss / statistics library; raises (never falls back) when it is not built."""
-    global _gls
-    if _gls is None:
-        _gls = _load(LIBS["gls"])
-    return _gls
-
-
-# libgab's and libgls's launches together: what bench.py's roofline.all_kernels is built from
-launch_profile_enable = partial(profile_enable, ("gab", "gls"))
-launch_profile_read = partial(profile_read, ("gab", "gls"))
-gsr_error = partial(last_error, "gsr")
-gab_error = partial(last_error, "gab")
-gls_error = partial(last_error, "gls")
+gls = _register("gls", GLS_SYMBOLS, GLS_ABI_VERSION)
+GLS_LIB_PATH = LIBS["gls"].path   # bench.py and _host.py read it
 
 
 # ------------------------------------------------------------------------------------------------
 # libgmr_hip.so : the mesh overlay's triangle rasterizer and antialias (include/gmr.h).  Loaded only by mesh_raster.py and
 # mesh_renderer.py: the splat path never maps it.
 # ------------------------------------------------------------------------------------------------
-GMR_LIB_PATH = _lib_path("gmr")
 GMR_SYMBOLS = {
     "gmr_abi_version": (C.c_int, []),
     "gmr_last_error": (C.c_char_p, []),
@@ -374,11 +354,8 @@ GMR_SYMBOLS = {
 GMR_ABI_VERSION = 2
 GMR_MAX_TRIANGLES = (1 << 24) - 1   # include/gmr.h: triangle_id + 1 is stored as an exact float
 
-LIBS["gmr"] = LibSpec("gmr", GMR_LIB_PATH, GMR_SYMBOLS, GMR_ABI_VERSION)
-
-# ABI 2, include/gmr_overlay.h (which gmr.h includes): the shaded overlay of mesh_renderer.py.  A table of its own because GMR_SYMBOLS is
-# pinned to the five declarations of gmr.h itself (tests/test_mesh_raster_cpu.py), like LIBS to its six tags; gmr() checks both tables, so
-# a library built before these entries raises at load time
+# ABI 2, include/gmr_overlay.h (which gmr.h includes): the shaded overlay of mesh_renderer.py.  One dict per header; the library is
+# registered with their union, so a file built before these entries raises at load time
 GMR_LIGHT_CONSTANT, GMR_LIGHT_FRONT = 0, 1   # include/gmr_overlay.h
 GMR_MAT_ROWS, GMR_MAT_CAMERA = 0, 1
 GMR_MAX_MAPS = 4
@@ -395,25 +372,13 @@ GMR_OVERLAY_SYMBOLS = {
     "gmr_resize_flip": (C.c_int, [C.c_int32] * 6 + [C.POINTER(GmrMap), _P]),
     "gmr_compose_overlay": (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_float, C.c_float, _P, _P, _P]),
 }
-_gmr = None
 
-
-def gmr():
-    """The mesh rasterizer library; raises (never falls back) when it is not built or lacks an entry of either table."""
-    global _gmr
-    if _gmr is None:
-        spec = LIBS["gmr"]
-        _gmr = _load(spec._replace(symbols={**spec.symbols, **GMR_OVERLAY_SYMBOLS}))
-    return _gmr
-
-
-gmr_error = partial(last_error, "gmr")
+gmr = _register("gmr", {**GMR_SYMBOLS, **GMR_OVERLAY_SYMBOLS}, GMR_ABI_VERSION)
 
 
 # ------------------------------------------------------------------------------------------------
 # libgop_hip.so : the fused Adam step (include/gop.h).  Loaded only by optim.py, at the first step on device tensors.
 # ------------------------------------------------------------------------------------------------
-GOP_LIB_PATH = _lib_path("gop")
 GOP_ABI_VERSION = 1
 GOP_MAX_TENSORS = 32   # include/gop.h: tensors per launch
 GOP_SLAB = 2048        # include/gop.h: elements per workgroup
@@ -433,27 +398,12 @@ GOP_SYMBOLS = {
     **_profile_symbols("gop"),
 }
 
-LIBS["gop"] = LibSpec("gop", GOP_LIB_PATH, GOP_SYMBOLS, GOP_ABI_VERSION)
-_gop = None
-
-
-def gop():
-    """The optimizer library; raises (never falls back) when it is not built."""
-    global _gop
-    if _gop is None:
-        _gop = _load(LIBS["gop"])
-    return _gop
-
-
-gop_error = partial(last_error, "gop")
-gop_profile_enable = partial(profile_enable, ("gop",))
-gop_profile_read = partial(profile_read, ("gop",))
+gop = _register("gop", GOP_SYMBOLS, GOP_ABI_VERSION)
 
 
 # ------------------------------------------------------------------------------------------------
 # libgrl_hip.so : the fused splat regularisers (include/grl.h).  Loaded only by loss.splat_regularizers, at the first call on device tensors.
 # ------------------------------------------------------------------------------------------------
-GRL_LIB_PATH = _lib_path("grl")
 GRL_ABI_VERSION = 1
 GRL_SLAB = 1024               # include/grl.h: splats per workgroup
 GRL_MAX_SPLATS = 1 << 24      # include/grl.h: P must stay below this (the count is an exact float)
@@ -467,31 +417,12 @@ GRL_SYMBOLS = {
     **_profile_symbols("grl"),
 }
 
-LIBS["grl"] = LibSpec("grl", GRL_LIB_PATH, GRL_SYMBOLS, GRL_ABI_VERSION)
-_grl = None
-
-
-def grl():
-    """The regulariser library; raises (never falls back) when it is not built."""
-    global _grl
-    if _grl is None:
-        _grl = _load(LIBS["grl"])
-    return _grl
-
-
-grl_error = partial(last_error, "grl")
-grl_profile_enable = partial(profile_enable, ("grl",))
-grl_profile_read = partial(profile_read, ("grl",))
+grl = _register("grl", GRL_SYMBOLS, GRL_ABI_VERSION)
 
 
 # ------------------------------------------------------------------------------------------------
 # libgdc_hip.so : adaptive density control (include/gdc.h).  Loaded only by densify.py and knn.py, at the first call on device tensors.
 # ------------------------------------------------------------------------------------------------
-#: tag -> LibSpec of the libraries added after LIBS was pinned to its six tags (tests/test_lib_loader_cpu.py); handle(), last_error() and the
-#: profile shims take these tags exactly like those of LIBS, and build() checks both tables
-MORE_LIBS = {}
-
-GDC_LIB_PATH = _lib_path("gdc")
 GDC_ABI_VERSION = 2
 GDC_CHUNK = 256                # include/gdc.h: splats per workgroup of the scan
 GDC_MAX_TENSORS = 24           # include/gdc.h: tensors one gather launch moves
@@ -526,31 +457,12 @@ GDC_SYMBOLS = {
     **_profile_symbols("gdc"),
 }
 
-MORE_LIBS["gdc"] = LibSpec("gdc", GDC_LIB_PATH, GDC_SYMBOLS, GDC_ABI_VERSION)
-_gdc = None
-
-
-def gdc():
-    """The density-control library; raises (never falls back) when it is not built."""
-    global _gdc
-    if _gdc is None:
-        _gdc = _load(MORE_LIBS["gdc"])
-    return _gdc
-
-
-gdc_error = partial(last_error, "gdc")
-gdc_profile_enable = partial(profile_enable, ("gdc",))
-gdc_profile_read = partial(profile_read, ("gdc",))
+gdc = _register("gdc", GDC_SYMBOLS, GDC_ABI_VERSION)
 
 
 # ------------------------------------------------------------------------------------------------
 # libgev_hip.so : evaluation and export (include/gev.h).  Loaded only by evaluate.py, at the first call on device tensors.
 # ------------------------------------------------------------------------------------------------
-#: tag -> LibSpec of the libraries added after MORE_LIBS was pinned to ["gdc"] in its turn (tests/test_densify_cpu.py, tests/test_knn_cpu.py);
-#: the third table works exactly like the other two: handle(), last_error() and the profile shims take its tags, and build() checks all three
-EVAL_LIBS = {}
-
-GEV_LIB_PATH = _lib_path("gev")
 GEV_ABI_VERSION = 1
 GEV_F32_PLANAR, GEV_U8_INTERLEAVED = 0, 1          # include/gev.h: layout of one image of a pair
 GEV_RAW, GEV_CLAMP, GEV_PNG8 = 0, 1, 2             # include/gev.h: load transform of a planar fp32 image
@@ -567,31 +479,12 @@ GEV_SYMBOLS = {
     **_profile_symbols("gev"),
 }
 
-EVAL_LIBS["gev"] = LibSpec("gev", GEV_LIB_PATH, GEV_SYMBOLS, GEV_ABI_VERSION)
-_gev = None
-
-
-def gev():
-    """The evaluation library; raises (never falls back) when it is not built."""
-    global _gev
-    if _gev is None:
-        _gev = _load(EVAL_LIBS["gev"])
-    return _gev
-
-
-gev_error = partial(last_error, "gev")
-gev_profile_enable = partial(profile_enable, ("gev",))
-gev_profile_read = partial(profile_read, ("gev",))
+gev = _register("gev", GEV_SYMBOLS, GEV_ABI_VERSION)
 
 
 # ------------------------------------------------------------------------------------------------
 # libgfs_hip.so : the resident frame store (include/gfs.h).  Loaded only by frames.py, at the first ingest or fetch on device tensors.
 # ------------------------------------------------------------------------------------------------
-#: tag -> LibSpec of the libraries added after EVAL_LIBS was pinned to ["gev"] in its turn (tests/test_eval_cpu.py); the fourth table works
-#: exactly like the other three: handle(), last_error() and the profile shims take its tags, and build() checks all four
-FRAME_LIBS = {}
-
-GFS_LIB_PATH = _lib_path("gfs")
 GFS_ABI_VERSION = 2
 GFS_E_RANGE = -3               # include/gfs.h: a host index outside the store
 GFS_TABLE_ENTRIES = 256        # include/gfs.h: floats of the byte-to-float table
@@ -612,32 +505,13 @@ GFS_SYMBOLS = {
     **_profile_symbols("gfs"),
 }
 
-FRAME_LIBS["gfs"] = LibSpec("gfs", GFS_LIB_PATH, GFS_SYMBOLS, GFS_ABI_VERSION)
-_gfs = None
-
-
-def gfs():
-    """The frame-store library; raises (never falls back) when it is not built."""
-    global _gfs
-    if _gfs is None:
-        _gfs = _load(FRAME_LIBS["gfs"])
-    return _gfs
-
-
-gfs_error = partial(last_error, "gfs")
-gfs_profile_enable = partial(profile_enable, ("gfs",))
-gfs_profile_read = partial(profile_read, ("gfs",))
+gfs = _register("gfs", GFS_SYMBOLS, GFS_ABI_VERSION)
 
 
 # ------------------------------------------------------------------------------------------------
 # libgms_hip.so : the fused metric-space regularisers (include/gms.h).  Loaded only by loss.metric_regularizers, at the first call on device
 # tensors.
 # ------------------------------------------------------------------------------------------------
-#: tag -> LibSpec of the libraries added after FRAME_LIBS was pinned to ["gfs"] in its turn (tests/test_frames_cpu.py); the fifth table works
-#: exactly like the other four: handle(), last_error() and the profile shims take its tags, and build() checks all five
-REG_LIBS = {}
-
-GMS_LIB_PATH = _lib_path("gms")
 GMS_ABI_VERSION = 1
 GMS_SLAB = 1024               # include/gms.h: splats per workgroup
 GMS_MAX_SPLATS = 1 << 24      # include/gms.h: P must stay below this (the count is an exact float)
@@ -652,31 +526,12 @@ GMS_SYMBOLS = {
     **_profile_symbols("gms"),
 }
 
-REG_LIBS["gms"] = LibSpec("gms", GMS_LIB_PATH, GMS_SYMBOLS, GMS_ABI_VERSION)
-_gms = None
-
-
-def gms():
-    """The metric-space regulariser library; raises (never falls back) when it is not built."""
-    global _gms
-    if _gms is None:
-        _gms = _load(REG_LIBS["gms"])
-    return _gms
-
-
-gms_error = partial(last_error, "gms")
-gms_profile_enable = partial(profile_enable, ("gms",))
-gms_profile_read = partial(profile_read, ("gms",))
+gms = _register("gms", GMS_SYMBOLS, GMS_ABI_VERSION)
 
 
 # ------------------------------------------------------------------------------------------------
 # libglp_hip.so : LPIPS for evaluation (include/glp.h).  Loaded only by lpips.py, at the first call on device tensors.
 # ------------------------------------------------------------------------------------------------
-#: tag -> LibSpec of the libraries added after REG_LIBS was pinned to ["gms"] in its turn (tests/test_metric_reg_cpu.py); the sixth table works
-#: exactly like the other five: handle(), last_error() and the profile shims take its tags, and build() checks all six
-LPIPS_LIBS = {}
-
-GLP_LIB_PATH = _lib_path("glp")
 GLP_ABI_VERSION = 1
 GLP_NET_ALEX, GLP_NET_VGG = 0, 1   # include/glp.h: the two backbones
 GLP_TAPS = 5                       # include/glp.h: taps of either net
@@ -703,18 +558,20 @@ GLP_SYMBOLS = {
     **_profile_symbols("glp"),
 }
 
-LPIPS_LIBS["glp"] = LibSpec("glp", GLP_LIB_PATH, GLP_SYMBOLS, GLP_ABI_VERSION)
-_glp = None
+glp = _register("glp", GLP_SYMBOLS, GLP_ABI_VERSION)
 
 
-def glp():
-    """The LPIPS library; raises (never falls back) when it is not built."""
-    global _glp
-    if _glp is None:
-        _glp = _load(LPIPS_LIBS["glp"])
-    return _glp
+# ------------------------------------------------------------------------------------------------
+# per-library shims, made from the table: <tag>_error() for every library, <tag>_profile_enable(on) / <tag>_profile_read() for every one that
+# exports csrc/launch_prof.h's entries (libgsr does not: gsr_profile_enable / gsr_profile_read above are its slot-based twins)
+# ------------------------------------------------------------------------------------------------
+for _tag, _spec in LIBS.items():
+    globals()[_tag + "_error"] = partial(last_error, _tag)
+    if _tag + "_profile_collect" in _spec.symbols:
+        globals()[_tag + "_profile_enable"] = partial(profile_enable, (_tag,))
+        globals()[_tag + "_profile_read"] = partial(profile_read, (_tag,))
+del _tag, _spec
 
-
-glp_error = partial(last_error, "glp")
-glp_profile_enable = partial(profile_enable, ("glp",))
-glp_profile_read = partial(profile_read, ("glp",))
+# libgab's and libgls's launches together: what bench.py's roofline.all_kernels is built from
+launch_profile_enable = partial(profile_enable, ("gab", "gls"))
+launch_profile_read = partial(profile_read, ("gab", "gls"))

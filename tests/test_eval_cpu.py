@@ -31,39 +31,14 @@ def test_pins_file_holds_the_four_pairs_in_range():
     assert all(PINS[k].dtype.kind in "fu" for k in PINS.files)
 
 
-# ---- the library's description ------------------------------------------------------------------------------------------------------------
+# ---- the constants _lib.py mirrors (names, ABI and load failures: tests/test_lib_loader_cpu.py) --------------------------------------------
 def test_description_header_and_library_agree():
     txt = open(os.path.join(ROOT, "include", "gev.h")).read()
-    code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
-    names = set(re.findall(r"\b(gev_[a-z0-9_]+)\s*\(", code))
-    abi = int(re.search(r"#define\s+GEV_ABI_VERSION\s+(\d+)", txt).group(1))
-    spec = _lib.EVAL_LIBS["gev"]
-    assert list(_lib.EVAL_LIBS) == ["gev"] and "gev" not in _lib.LIBS and "gev" not in _lib.MORE_LIBS
-    assert spec.tag == "gev" and spec.path == _lib.GEV_LIB_PATH and spec.symbols is _lib.GEV_SYMBOLS and spec.abi == _lib.GEV_ABI_VERSION
-    assert names == set(spec.symbols), sorted(names ^ set(spec.symbols))
-    assert abi == spec.abi
-    lib = _lib.gev()
-    assert lib.gev_abi_version() == abi and _lib.handle("gev") is lib and _lib.gev() is lib
-    assert isinstance(_lib.last_error("gev"), str)
     for name, value in re.findall(r"#define\s+(GEV_[A-Z0-9_]+)\s+\(?(-?\d+)\)?", txt):   # the constants _lib.py mirrors
         if hasattr(_lib, name):
             assert getattr(_lib, name) == int(value), name
     for name in ("GEV_F32_PLANAR", "GEV_U8_INTERLEAVED", "GEV_RAW", "GEV_CLAMP", "GEV_PNG8", "GEV_PSNR_PER_CHANNEL", "GEV_PSNR_PER_IMAGE"):
         assert hasattr(_lib, name) and re.search(r"#define\s+%s\s" % name, txt), name
-
-
-def test_load_failures_read_as_for_every_library():
-    spec, real = _lib.EVAL_LIBS["gev"], _lib.gev()
-    missing = os.path.join(ROOT, "no_such_dir", "libgev_hip.so")
-    with pytest.raises(RuntimeError) as e:
-        _lib._load(spec._replace(path=missing))
-    assert missing in str(e.value) and "build()" in str(e.value)
-    with pytest.raises(RuntimeError) as e:
-        _lib._load(spec._replace(abi=spec.abi + 1))
-    assert str(e.value) == "gev ABI version %d != %d" % (spec.abi, spec.abi + 1)
-    with pytest.raises(AttributeError):
-        _lib._load(spec._replace(symbols={**spec.symbols, "gev_no_such_entry": (C.c_int, [])}))
-    assert _lib.gev() is real
 
 
 def test_argument_checks_need_no_gpu():
@@ -87,11 +62,11 @@ def test_bare_import_maps_no_evaluation_library():
             "import gaussianavatars_amd\n"
             "from gaussianavatars_amd import _lib\n"
             "import gaussianavatars_amd.evaluate, gaussianavatars_amd.patch\n"
-            "print('CACHE', _lib._gev)\n"
-            "print('MAPPED', 'libgev_hip.so' in open('/proc/self/maps').read())\n" % ROOT)
+            "print('MAPPED', 'libgev_hip.so' in open('/proc/self/maps').read())\n"
+            "print('LOADED', _lib.gev() is not None and 'libgev_hip.so' in open('/proc/self/maps').read())\n" % ROOT)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
-    assert "CACHE None" in r.stdout and "MAPPED False" in r.stdout, r.stdout
+    assert "MAPPED False" in r.stdout and "LOADED True" in r.stdout, r.stdout
 
 
 # ---- the composed-torch path against the pins -----------------------------------------------------------------------------------------------

@@ -28,20 +28,10 @@ needs_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "scene")), re
 PINS = FC.pins()
 
 
-# ---- the library's description ------------------------------------------------------------------------------------------------------------
+# ---- the constants _lib.py mirrors and the stride rule (names, ABI and load failures: tests/test_lib_loader_cpu.py) ------------------------
 def test_description_header_and_library_agree():
     txt = open(os.path.join(ROOT, "include", "gfs.h")).read()
-    code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
-    names = set(re.findall(r"\b(gfs_[a-z0-9_]+)\s*\(", code))
-    abi = int(re.search(r"#define\s+GFS_ABI_VERSION\s+(\d+)", txt).group(1))
-    spec = _lib.FRAME_LIBS["gfs"]
-    assert list(_lib.FRAME_LIBS) == ["gfs"] and not any("gfs" in t for t in (_lib.LIBS, _lib.MORE_LIBS, _lib.EVAL_LIBS))
-    assert spec.tag == "gfs" and spec.path == _lib.GFS_LIB_PATH and spec.symbols is _lib.GFS_SYMBOLS and spec.abi == _lib.GFS_ABI_VERSION
-    assert names == set(spec.symbols), sorted(names ^ set(spec.symbols))
-    assert abi == spec.abi
     lib = _lib.gfs()
-    assert lib.gfs_abi_version() == abi and _lib.handle("gfs") is lib and _lib.gfs() is lib
-    assert isinstance(_lib.last_error("gfs"), str)
     mirrored = 0
     for name, value in re.findall(r"#define\s+(GFS_[A-Z0-9_]+)\s+\(?(-?\d+)\)?", txt):   # the constants _lib.py mirrors
         if hasattr(_lib, name):
@@ -82,11 +72,11 @@ def test_bare_import_maps_no_frame_library():
             "import gaussianavatars_amd\n"
             "from gaussianavatars_amd import _lib\n"
             "import gaussianavatars_amd.frames, gaussianavatars_amd.patch, gaussianavatars_amd.gaussian_renderer\n"
-            "print('CACHE', _lib._gfs)\n"
-            "print('MAPPED', 'libgfs_hip.so' in open('/proc/self/maps').read())\n" % ROOT)
+            "print('MAPPED', 'libgfs_hip.so' in open('/proc/self/maps').read())\n"
+            "print('LOADED', _lib.gfs() is not None and 'libgfs_hip.so' in open('/proc/self/maps').read())\n" % ROOT)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
-    assert "CACHE None" in r.stdout and "MAPPED False" in r.stdout, r.stdout
+    assert "MAPPED False" in r.stdout and "LOADED True" in r.stdout, r.stdout
 
 
 # ---- the host restatement against the pins ---------------------------------------------------------------------------------------------------

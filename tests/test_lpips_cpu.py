@@ -77,28 +77,16 @@ def test_measured_constants_are_the_bars():
     assert "%.3e" % LC.CONV_ERR_FP32 in design and "%.3e" % LC.SCALAR_ERR_FP32 in design
 
 
-# ---- the library's description -------------------------------------------------------------------------------------------------------------
+# ---- the constants _lib.py mirrors (names in header order, ABI and load failures: tests/test_lib_loader_cpu.py) -----------------------------
 def test_description_header_and_library_agree():
     txt = open(os.path.join(ROOT, "include", "glp.h")).read()
-    code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
-    names = re.findall(r"\b(glp_[a-z0-9_]+)\s*\(", code)
-    spec = _lib.LPIPS_LIBS["glp"]
-    assert list(_lib.LPIPS_LIBS) == ["glp"]
-    assert not any("glp" in table for table in (_lib.LIBS, _lib.MORE_LIBS, _lib.EVAL_LIBS, _lib.FRAME_LIBS, _lib.REG_LIBS))
-    assert spec.tag == "glp" and spec.path == _lib.GLP_LIB_PATH and spec.symbols is _lib.GLP_SYMBOLS and list(spec.symbols) == names
-    abi = int(re.search(r"#define\s+GLP_ABI_VERSION\s+(\d+)", txt).group(1))
     lib = _lib.glp()
-    assert lib.glp_abi_version() == abi == spec.abi == _lib.GLP_ABI_VERSION and _lib.handle("glp") is lib and isinstance(_lib.glp_error(), str)
     for name, value in re.findall(r"#define\s+(GLP_[A-Z0-9_]+)\s+\(?(-?\d+)\)?", txt):
         if name not in ("GLP_OK", "GLP_E_ARG", "GLP_E_HIP"):
             assert getattr(_lib, name) == int(value), name
     assert lib.glp_net_convs(_lib.GLP_NET_ALEX) == 5 and lib.glp_net_convs(_lib.GLP_NET_VGG) == _lib.GLP_MAX_CONVS
     mk = open(os.path.join(ROOT, "gaussianavatars_amd", "csrc", "Makefile")).read()
     assert re.search(r"^SINGLE := .*\bglp\b", mk, flags=re.M) and re.search(r"^glp_kernels\.o: CONTRACT := -ffp-contract=fast$", mk, flags=re.M)
-    assert "_lib.LPIPS_LIBS" in open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    with pytest.raises(RuntimeError) as e:
-        _lib._load(spec._replace(abi=spec.abi + 1))
-    assert str(e.value) == "glp ABI version %d != %d" % (spec.abi, spec.abi + 1)
 
 
 def test_layer_tables_of_package_library_and_helper_agree():
@@ -120,11 +108,11 @@ def test_bare_import_maps_no_lpips_library():
             "import gaussianavatars_amd\n"
             "from gaussianavatars_amd import _lib\n"
             "import gaussianavatars_amd.lpips, gaussianavatars_amd.evaluate, gaussianavatars_amd.patch\n"
-            "print('CACHE', _lib._glp)\n"
-            "print('MAPPED', 'libglp_hip.so' in open('/proc/self/maps').read())\n" % ROOT)
+            "print('MAPPED', 'libglp_hip.so' in open('/proc/self/maps').read())\n"
+            "print('LOADED', _lib.glp() is not None and 'libglp_hip.so' in open('/proc/self/maps').read())\n" % ROOT)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
-    assert "CACHE None" in r.stdout and "MAPPED False" in r.stdout, r.stdout
+    assert "MAPPED False" in r.stdout and "LOADED True" in r.stdout, r.stdout
 
 
 def test_argument_checks_need_no_gpu():

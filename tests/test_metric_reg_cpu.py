@@ -30,20 +30,10 @@ def test_description_header_and_library_agree():
     from gaussianavatars_amd import _lib
 
     txt = open(os.path.join(ROOT, "include", "gms.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    names = re.findall(r"\b(gms_[a-z0-9_]+)\s*\(", code)
-    assert names == ["gms_abi_version", "gms_last_error", "gms_scratch_bytes", "gms_forward", "gms_backward", "gms_profile_enable",
-                     "gms_profile_collect", "gms_profile_entry", "gms_profile_reset"]
-    spec = _lib.REG_LIBS["gms"]
-    assert list(_lib.REG_LIBS) == ["gms"]
-    assert not any("gms" in table for table in (_lib.LIBS, _lib.MORE_LIBS, _lib.EVAL_LIBS, _lib.FRAME_LIBS))
-    assert spec.tag == "gms" and spec.path == _lib.GMS_LIB_PATH and spec.symbols is _lib.GMS_SYMBOLS and list(spec.symbols) == names
-    abi = int(re.search(r"#define\s+GMS_ABI_VERSION\s+(\d+)", txt).group(1))
-    lib = _lib.gms()
-    for n in names:
-        assert hasattr(lib, n), n
-    assert lib.gms_abi_version() == abi == spec.abi == _lib.GMS_ABI_VERSION == 1
-    assert _lib.handle("gms") is lib and isinstance(_lib.gms_error(), str)
+    # header, description and built file agree name by name, in order: tests/test_lib_loader_cpu.py.  Here, what the names are
+    assert list(_lib.LIBS["gms"].symbols) == ["gms_abi_version", "gms_last_error", "gms_scratch_bytes", "gms_forward", "gms_backward",
+                                              "gms_profile_enable", "gms_profile_collect", "gms_profile_entry", "gms_profile_reset"]
+    assert _lib.gms().gms_abi_version() == _lib.GMS_ABI_VERSION == 1 and isinstance(_lib.gms_error(), str)
     for name in ("GMS_SLAB", "GMS_ROW_BYTES"):
         assert int(re.search(r"#define\s+%s\s+(\d+)" % name, txt).group(1)) == getattr(_lib, name)
     assert _lib.GMS_MAX_SPLATS == 1 << 24 and re.search(r"#define\s+GMS_MAX_SPLATS\s+\(1 << 24\)", txt)
@@ -51,8 +41,6 @@ def test_description_header_and_library_agree():
     assert _lib.grl().grl_abi_version() == 1 and _lib.gls().gls_abi_version() == 4
     mk = open(os.path.join(ROOT, "gaussianavatars_amd", "csrc", "Makefile")).read()
     assert re.search(r"^SINGLE := .*\bgms\b", mk, flags=re.M) and re.search(r"^gms_kernels\.o: CONTRACT := -ffp-contract=off$", mk, flags=re.M)
-    entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert "_lib.REG_LIBS" in entry
 
 
 def test_bare_import_maps_no_metric_library():
@@ -60,11 +48,11 @@ def test_bare_import_maps_no_metric_library():
             "import gaussianavatars_amd\n"
             "from gaussianavatars_amd import _lib\n"
             "import gaussianavatars_amd.loss, gaussianavatars_amd.patch\n"
-            "print('CACHE', _lib._gms)\n"
-            "print('MAPPED', 'libgms_hip.so' in open('/proc/self/maps').read())\n" % ROOT)
+            "print('MAPPED', 'libgms_hip.so' in open('/proc/self/maps').read())\n"
+            "print('LOADED', _lib.gms() is not None and 'libgms_hip.so' in open('/proc/self/maps').read())\n" % ROOT)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
-    assert "CACHE None" in r.stdout and "MAPPED False" in r.stdout, r.stdout
+    assert "MAPPED False" in r.stdout and "LOADED True" in r.stdout, r.stdout
 
 
 def test_host_side_argument_checks_launch_nothing():

@@ -19,7 +19,7 @@ def test_header_description_and_library_export_the_new_entries():
     txt = open(os.path.join(ROOT, "include", "gdc.h")).read()
     code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
     declared = set(re.findall(r"\b(gdc_[a-z0-9_]+)\s*\(", code))
-    assert int(re.search(r"#define\s+GDC_ABI_VERSION\s+(\d+)", txt).group(1)) == 2 == _lib.GDC_ABI_VERSION == _lib.MORE_LIBS["gdc"].abi
+    assert int(re.search(r"#define\s+GDC_ABI_VERSION\s+(\d+)", txt).group(1)) == 2 == _lib.GDC_ABI_VERSION == _lib.LIBS["gdc"].abi
     lib = _lib.gdc()
     assert lib.gdc_abi_version() == 2
     for name in NEW:
