@@ -316,6 +316,30 @@ GAB_ABI_VERSION = 5
 gab = _register("gab", GAB_SYMBOLS, GAB_ABI_VERSION, "GAB_LIB")
 GAB_LIB_PATH = LIBS["gab"].path   # bench.py and _host.py read it
 
+#: every symbol include/gab_landmarks.h declares -> (restype, argtypes): additive exports of the same library (gab.h's list is frozen at ABI 5)
+GAB_LANDMARK_SYMBOLS = {
+    "gab_landmarks_forward": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    "gab_landmarks_backward": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, _P]),
+    "gab_root_joint": (C.c_int, [C.POINTER(GabRig), _P, _P, _P]),
+    "gab_root_center": (C.c_int, [C.c_int32, _P, _P, _P, _P, _P]),
+    "gab_root_center_backward": (C.c_int, [C.POINTER(GabRig), _P, _P, _P, _P]),
+}
+_gab_landmarks = None
+
+
+def gab_landmarks():
+    """libgab_hip.so -- gab()'s handle -- with the entries of include/gab_landmarks.h resolved and typed at the first call; raises (never falls
+    back) when the file that is built does not export them."""
+    global _gab_landmarks
+    if _gab_landmarks is None:
+        lib = gab()
+        for name, (res, args) in GAB_LANDMARK_SYMBOLS.items():
+            fn = getattr(lib, name)  # AttributeError: a library built before these entries
+            fn.restype = res
+            fn.argtypes = args
+        _gab_landmarks = lib
+    return _gab_landmarks
+
 
 # ------------------------------------------------------------------------------------------------
 # libgls_hip.so : fused L1 + SSIM loss and densification statistics (include/gls.h)

@@ -322,6 +322,186 @@ def flame_forward_timestep(head, flame_param: dict, t: int):
 
 
 # -------------------------------------------------------------------------------------------------
+# landmarks and root-centred output (FlameHead.forward's two other switches, flame_model/flame.py:532-553)
+# -------------------------------------------------------------------------------------------------
+def check_landmark_embedding(faces, lmk_faces_idx, lmk_bary_coords):
+    """The host-side check of an embedding, once, when it is attached (the kernels cannot report a bad face index without a read-back):
+    -> (lmk_faces_idx (L,) long, lmk_bary_coords (L,3) fp32) from either layout, (L,) / (L,3) or the reference's (1,L) / (1,L,3)."""
+    idx = torch.as_tensor(lmk_faces_idx)
+    bary = torch.as_tensor(lmk_bary_coords)
+    if idx.dtype.is_floating_point or idx.dtype is torch.bool:
+        raise ValueError(f"lmk_faces_idx must hold integer face indices (got {idx.dtype})")
+    if idx.dim() == 2 and idx.shape[0] == 1:
+        idx = idx[0]
+    if bary.dim() == 3 and bary.shape[0] == 1:
+        bary = bary[0]
+    if idx.dim() != 1 or tuple(bary.shape) != (idx.shape[0], 3):
+        raise ValueError(f"landmark embedding: expected face indices (L,) or (1,L) and barycentric coordinates (L,3) or (1,L,3), got "
+                         f"{tuple(torch.as_tensor(lmk_faces_idx).shape)} and {tuple(torch.as_tensor(lmk_bary_coords).shape)}")
+    F = int(faces.shape[0])
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= F):
+        bad = [int(i) for i in torch.nonzero((idx < 0) | (idx >= F)).reshape(-1)[:4].tolist()]
+        raise ValueError(f"landmark embedding: lmk_faces_idx must lie in [0, {F}); landmarks {bad} hold {[int(idx[i]) for i in bad]}")
+    return idx.long().contiguous(), bary.to(torch.float32).contiguous()
+
+
+def landmark_csr(faces: torch.Tensor, lmk_face: torch.Tensor, num_verts: int):
+    """(lmk_order int32 (3L,), vert_begin int32 (V+1,)) for gab_landmarks_backward: the corner numbers 3 l + k of the embedding sorted by
+    (vertex, l, k) -- a stable sort of the corners, which already are in (l, k) order, by their vertex -- and every vertex's row in that list."""
+    corner_vertex = faces.detach().long()[lmk_face.detach().reshape(-1).long()].reshape(-1)   # vertex of corner 3 l + k
+    order = torch.sort(corner_vertex, stable=True).indices.to(torch.int32).contiguous()
+    vert_begin = torch.zeros(num_verts + 1, dtype=torch.int32, device=corner_vertex.device)
+    vert_begin[1:] = torch.cumsum(torch.bincount(corner_vertex, minlength=num_verts), 0).to(torch.int32)
+    return order, vert_begin
+
+
+def _landmark_tables(head):
+    """What the two landmark entries read, as device tensors kept on the head next to the prepared rig: (faces, is64, lmk_face int32 (L,),
+    lmk_bary fp32 (L,3), lmk_order, vert_begin).  Built (and the embedding checked on the host) at the first call, re-made when the faces or
+    the embedding are replaced or modified in place."""
+    idx, bary, faces = getattr(head, "full_lmk_faces_idx", None), getattr(head, "full_lmk_bary_coords", None), head.faces
+    if idx is None or bary is None:
+        raise ValueError("this FlameHead has no landmark embedding: call attach_landmarks(lmk_faces_idx, lmk_bary_coords) first")
+    key = (faces.data_ptr(), faces._version, idx.data_ptr(), idx._version, bary.data_ptr(), bary._version, int(head.v_template.shape[0]))
+    c = head.__dict__.get("_gab_landmarks")
+    if c is None or c[0] != key:
+        _need_cuda(faces, "faces")
+        li, lb = check_landmark_embedding(faces, idx, bary)
+        fi, is64 = _idx(faces)
+        li, lb = li.to(faces.device), lb.to(faces.device)
+        order, begin = landmark_csr(fi, li, key[-1])
+        head.__dict__["_gab_landmarks"] = c = (key, (fi, is64, li.to(torch.int32).contiguous(), lb, order, begin), (faces, idx, bary))
+    return c[1]
+
+
+def landmarks_backward(head, d_landmarks, into=None):
+    """gab_landmarks_backward on its own: the (V,3) gradient of the vertices for d_landmarks (L,3); `into` -- a contiguous fp32 (V,3) gradient
+    from another consumer of the vertices -- receives the sums in place instead (accumulate = 1)."""
+    fi, is64, lf, lb, order, begin = _landmark_tables(head)
+    g = _f32(d_landmarks).reshape(-1, 3)
+    V, F, L = int(head.v_template.shape[0]), int(fi.shape[0]), int(lf.shape[0])
+    if g.shape[0] != L:
+        raise RuntimeError(f"d_landmarks must be ({L},3)")
+    dev = fi.device
+    if into is not None and not (_plain(into) and into.numel() == 3 * V):
+        raise RuntimeError("landmarks_backward: `into` must be a contiguous fp32 device tensor of (V,3)")
+    d_verts = torch.empty((V, 3), dtype=torch.float32, device=dev) if into is None else into
+    with _lib.on_device(dev):
+        _chk(_lib.gab_landmarks().gab_landmarks_backward(V, F, L, _p(fi), is64, _p(lf), _p(lb), _p(order), _p(begin), _p(g), _p(d_verts),
+                                                         0 if into is None else 1, _stream(dev)), "gab_landmarks_backward")
+    return d_verts
+
+
+class _Landmarks(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, head, verts):
+        ctx.set_materialize_grads(False)
+        _need_cuda(verts, "verts")
+        fi, is64, lf, lb, _, _ = _landmark_tables(head)
+        v = _f32(verts)
+        V, F, L = int(head.v_template.shape[0]), int(fi.shape[0]), int(lf.shape[0])
+        if v.numel() != 3 * V or v.shape[-1] != 3 or v.dim() not in (2, 3):
+            raise RuntimeError(f"landmarks: verts must be ({V},3) or (1,{V},3), got {tuple(verts.shape)}")
+        dev = v.device
+        out = torch.empty((L, 3) if v.dim() == 2 else (1, L, 3), dtype=torch.float32, device=dev)
+        with _lib.on_device(dev):
+            _chk(_lib.gab_landmarks().gab_landmarks_forward(V, F, L, _p(v), _p(fi), is64, _p(lf), _p(lb), _p(out), _stream(dev)), "gab_landmarks_forward")
+        ctx.head, ctx.shape = head, verts.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None
+        return None, landmarks_backward(ctx.head, g).view(ctx.shape)
+
+
+def landmarks(head, verts, impl=None):
+    """vertices2landmarks (flame_model/lbs.py:60-98) of the head's attached embedding: verts (V,3) or (1,V,3) -> (L,3) or (1,L,3).  Device fp32 runs
+    on the kernels (include/gab_landmarks.h: gab_landmarks_*); host tensors, other dtypes and impl="unfused" take unfused.landmarks."""
+    idx, bary = getattr(head, "full_lmk_faces_idx", None), getattr(head, "full_lmk_bary_coords", None)
+    if idx is None or bary is None:
+        raise ValueError("this FlameHead has no landmark embedding: call attach_landmarks(lmk_faces_idx, lmk_bary_coords) first")
+    if (impl or getattr(head, "impl", "fused")) == "unfused" or not verts.is_cuda or verts.dtype is not torch.float32:
+        from . import unfused
+
+        out = unfused.landmarks(verts if verts.dim() == 3 else verts[None], head.faces, idx, bary)
+        return out if verts.dim() == 3 else out[0]
+    return _Landmarks.apply(head, verts)
+
+
+def root_joint(head, v_shaped):
+    """J[:, 0] of flame_model/flame.py:533 before the translation: row 0 of the joint regression of v_shaped ((V,3) or (1,V,3)) -> (3,).  The root
+    rotates about itself, so lbs leaves it at its rest position (include/gab_landmarks.h: gab_root_joint).  No gradient: root_center is the differentiable entry."""
+    rig = _rig_struct(head)
+    vs = _f32(v_shaped)
+    _need_cuda(vs, "v_shaped")
+    if vs.numel() != 3 * rig.V:
+        raise RuntimeError("root_joint: v_shaped must be (V,3) or (1,V,3)")
+    dev = vs.device
+    root = torch.empty(3, dtype=torch.float32, device=dev)
+    with _lib.on_device(dev):
+        _chk(_lib.gab_landmarks().gab_root_joint(C.byref(rig), _p(vs), _p(root), _stream(dev)), "gab_root_joint")
+    return root
+
+
+class _RootCenter(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, head, verts, v_shaped, translation):
+        ctx.set_materialize_grads(False)
+        rig = _rig_struct(head)
+        v, tr = _f32(verts), _f32(translation).reshape(-1)
+        if v.numel() != 3 * rig.V or tr.numel() != 3:
+            raise RuntimeError("root_center is batch-1: verts (1,V,3), translation (1,3)")
+        dev = v.device
+        root = root_joint(head, v_shaped)
+        out = torch.empty_like(v)
+        with _lib.on_device(dev):
+            _chk(_lib.gab_landmarks().gab_root_center(rig.V, _p(v), _p(root), _p(tr), _p(out), _stream(dev)), "gab_root_center")
+        ctx.head, ctx.vs_shape, ctx.tr_shape = head, v_shaped.shape, translation.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None
+        rig = _rig_struct(ctx.head)
+        g = _f32(g)
+        dev = g.device
+        need = ctx.needs_input_grad   # (head, verts, v_shaped, translation)
+        d_vs = torch.empty(ctx.vs_shape, dtype=torch.float32, device=dev)
+        d_tr = torch.empty(3, dtype=torch.float32, device=dev) if need[3] else None
+        with _lib.on_device(dev):
+            _chk(_lib.gab_landmarks().gab_root_center_backward(C.byref(rig), _p(g), _p(d_vs), _p(d_tr), _stream(dev)), "gab_root_center_backward")
+        return None, g, d_vs if need[2] else None, None if d_tr is None else d_tr.view(ctx.tr_shape)
+
+
+def root_center(head, verts, v_shaped, translation):
+    """flame.py:532-537 for vertices computed with a ZERO translation: (verts - J[:, 0]) + translation, differentiable in all three."""
+    return _RootCenter.apply(head, verts, v_shaped, translation)
+
+
+def flame_head_outputs(head, shape, expr, rotation, neck, jaw, eyes, translation, static_offset=None, zero_centered_at_root_node=False,
+                       return_landmarks=True, return_verts_cano=False):
+    """FlameHead.forward (flame_model/flame.py:485-558) with any of its switches, batch 1, on the kernels: the reference's return value,
+    [vertices, (v_shaped), (landmarks)] or the vertices alone.  Gradients reach every input through the existing FLAME backward (the root
+    joint's arrive as the gradient of its second output, v_shaped)."""
+    if return_landmarks:
+        _landmark_tables(head)   # (no embedding: the ValueError before anything is launched)
+    if zero_centered_at_root_node:
+        verts, v_shaped = flame_forward(head, shape, expr, rotation, neck, jaw, eyes, torch.zeros_like(translation), static_offset)
+        verts = root_center(head, verts, v_shaped, translation)
+    else:
+        verts, v_shaped = flame_forward(head, shape, expr, rotation, neck, jaw, eyes, translation, static_offset)
+    ret = [verts]
+    if return_verts_cano:
+        ret.append(v_shaped)
+    if return_landmarks:
+        ret.append(landmarks(head, verts, impl="fused"))
+    return ret if len(ret) > 1 else ret[0]
+
+
+# -------------------------------------------------------------------------------------------------
 # per-face frames
 # -------------------------------------------------------------------------------------------------
 class _FaceFrames(torch.autograd.Function):

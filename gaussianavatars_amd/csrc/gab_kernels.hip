@@ -14,6 +14,7 @@
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 #include "../../include/gab.h"
+#include "../../include/gab_landmarks.h"
 #include "launch_prof.h"
 #include "lib_common.h"
 #include "bind_math.h"
@@ -1539,6 +1540,127 @@ __global__ __launch_bounds__(256) void k_zero_many(ZeroSpec z)
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < z.n[b]; i += gridDim.x * blockDim.x) p[i] = 0.f;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Landmarks (flame_model/lbs.py:60-98) and the root-centred output (flame_model/flame.py:532-537).  Launch-floor kernels: what matters
+// is that every sum has one fixed order (no same-address atomics) and that nothing is read back.
+// ---------------------------------------------------------------------------------------------
+// the three vertex indices of face f, or false when the face or one of its corners is outside the mesh (nothing is addressed through it)
+__device__ __forceinline__ bool face_corners(const void* __restrict__ faces, int is64, int V, int F, int f, long long* idx /*3*/)
+{
+    if (f < 0 || f >= F) return false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        idx[k] = index_at(faces, is64, 3ll * f + k);
+        if (idx[k] < 0 || idx[k] >= V) return false;
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_landmarks(int V, int F, int L, const float* __restrict__ verts, const void* __restrict__ faces, int is64,
+                                                    const int* __restrict__ lmk_face, const float* __restrict__ lmk_bary, float* __restrict__ landmarks)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;   // one lane per (landmark, coordinate)
+    if (i >= 3 * L) return;
+    const int l = i / 3, c = i - 3 * l;
+    long long idx[3];
+    float acc = __int_as_float(0x7fc00000);         // an embedding the host check should have refused: NaN, not a wild read
+    if (face_corners(faces, is64, V, F, lmk_face[l], idx)) {
+        acc = lmk_bary[3 * l] * verts[3 * idx[0] + c];
+        acc = fmaf(lmk_bary[3 * l + 1], verts[3 * idx[1] + c], acc);
+        acc = fmaf(lmk_bary[3 * l + 2], verts[3 * idx[2] + c], acc);
+    }
+    landmarks[i] = acc;
+}
+
+__global__ __launch_bounds__(256) void k_landmarks_bwd(int V, int F, int L, const void* __restrict__ faces, int is64, const int* __restrict__ lmk_face,
+                                                        const float* __restrict__ lmk_bary, const int* __restrict__ lmk_order,
+                                                        const int* __restrict__ vert_begin, const float* __restrict__ d_landmarks,
+                                                        float* __restrict__ d_verts, int accumulate)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x;   // one lane per vertex: its row of the CSR, in (l, k) order
+    if (v >= V) return;
+    int j = vert_begin[v], end = vert_begin[v + 1];
+    if (j < 0) j = 0;
+    if (end > 3 * L) end = 3 * L;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    for (; j < end; ++j) {
+        const int o = lmk_order[j];
+        if (o < 0 || o >= 3 * L) continue;
+        const int l = o / 3, f = lmk_face[l];
+        if (f < 0 || f >= F || index_at(faces, is64, 3ll * f + (o - 3 * l)) != (long long)v) continue;   // a stale table adds nothing
+        const float b = lmk_bary[o];
+        a0 = fmaf(b, d_landmarks[3 * l], a0);
+        a1 = fmaf(b, d_landmarks[3 * l + 1], a1);
+        a2 = fmaf(b, d_landmarks[3 * l + 2], a2);
+    }
+    if (accumulate) {
+        if (end > vert_begin[v]) { d_verts[3 * v] += a0; d_verts[3 * v + 1] += a1; d_verts[3 * v + 2] += a2; }
+    } else {
+        d_verts[3 * v] = a0; d_verts[3 * v + 1] = a1; d_verts[3 * v + 2] = a2;
+    }
+}
+
+// sum over v of w[v] * x[v][0..2] (w == nullptr: of x[v][0..2]) by one 1024-lane workgroup: wave k sums the k-th contiguous span of v (its lanes
+// stride through it, then the DPP tree), the 16 wave sums are added in wave order.  Valid in every lane after the call.
+__device__ __forceinline__ void block_sum3(int V, const float* __restrict__ w, const float* __restrict__ x, float (*red)[4], float* s /*3*/)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int span = (V + 15) / 16, begin = wid * span, end = min(V, begin + span);
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    for (int v = begin + lane; v < end; v += 64) {
+        const float wv = w ? w[v] : 1.f;
+        a0 = fmaf(wv, x[3 * v], a0);
+        a1 = fmaf(wv, x[3 * v + 1], a1);
+        a2 = fmaf(wv, x[3 * v + 2], a2);
+    }
+    a0 = wave_sum_hi(a0); a1 = wave_sum_hi(a1); a2 = wave_sum_hi(a2);
+    if (lane == 63) { red[wid][0] = a0; red[wid][1] = a1; red[wid][2] = a2; }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float t = 0.f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) t += red[k][c];
+        s[c] = t;
+    }
+}
+
+__global__ __launch_bounds__(1024) void k_root_joint(Rig rig, const float* __restrict__ v_shaped, float* __restrict__ root)
+{
+    __shared__ float red[16][4];
+    float s[3];
+    block_sum3(rig.V, rig.J_regressor, v_shaped, red, s);   // row 0 of the (5,V) regressor
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        if (threadIdx.x == c) root[c] = s[c];
+}
+
+__global__ __launch_bounds__(256) void k_root_center(int E, const float* verts, const float* __restrict__ root,
+                                                      const float* __restrict__ translation, float* out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= E) return;
+    const int c = i % 3;
+    out[i] = (verts[i] - root[c]) + translation[c];
+}
+
+__global__ __launch_bounds__(1024) void k_root_center_bwd(Rig rig, const float* __restrict__ d_out, float* __restrict__ d_v_shaped,
+                                                           float* __restrict__ d_translation)
+{
+    __shared__ float red[16][4];
+    float s[3];
+    block_sum3(rig.V, nullptr, d_out, red, s);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        if (d_translation && threadIdx.x == c) d_translation[c] = s[c];
+    for (int v = threadIdx.x; v < rig.V; v += 1024) {
+        const float w = -rig.J_regressor[v];
+        d_v_shaped[3 * v] = w * s[0];
+        d_v_shaped[3 * v + 1] = w * s[1];
+        d_v_shaped[3 * v + 2] = w * s[2];
+    }
+}
+
 }  // namespace gab
 
 // =================================================================================================
@@ -1934,6 +2056,65 @@ int gab_zero_buffers(int32_t count, float* const* buffers_host, const int32_t* s
     if (bx > 64) bx = 64;
     PROF_LAUNCH(gab::k_zero_many, dim3(bx, count), dim3(256), 0, (hipStream_t)stream_, z);
     LAUNCH_CHECK(GAB_E_HIP, "launch of k_zero_many failed");
+    return GAB_OK;
+}
+
+int gab_landmarks_forward(int32_t V, int32_t F, int32_t L, const float* verts, const void* faces, int32_t is64, const int32_t* lmk_face,
+                          const float* lmk_bary, float* landmarks, void* stream_)
+{
+    if (V <= 0 || F <= 0 || L < 0 || L > (1 << 28)) return fail(GAB_E_ARG, "gab_landmarks_forward: bad sizes");
+    if (L == 0) return GAB_OK;
+    if (!verts || !faces || !lmk_face || !lmk_bary || !landmarks) return fail(GAB_E_ARG, "gab_landmarks_forward: NULL buffer");
+    PROF_LAUNCH(gab::k_landmarks, dim3((3 * L + 255) / 256), dim3(256), 0, (hipStream_t)stream_, V, F, L, verts, faces, is64, lmk_face, lmk_bary,
+                       landmarks);
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_landmarks failed");
+    return GAB_OK;
+}
+
+int gab_landmarks_backward(int32_t V, int32_t F, int32_t L, const void* faces, int32_t is64, const int32_t* lmk_face, const float* lmk_bary,
+                           const int32_t* lmk_order, const int32_t* vert_begin, const float* d_landmarks, float* d_verts, int32_t accumulate,
+                           void* stream_)
+{
+    if (V <= 0 || F <= 0 || L < 0 || L > (1 << 28)) return fail(GAB_E_ARG, "gab_landmarks_backward: bad sizes");
+    if (!d_verts) return fail(GAB_E_ARG, "gab_landmarks_backward: d_verts is NULL");
+    hipStream_t st = (hipStream_t)stream_;
+    if (L == 0) {
+        if (!accumulate) HIP_TRY(hipMemsetAsync(d_verts, 0, (size_t)V * 3 * sizeof(float), st));
+        return GAB_OK;
+    }
+    if (!faces || !lmk_face || !lmk_bary || !lmk_order || !vert_begin || !d_landmarks) return fail(GAB_E_ARG, "gab_landmarks_backward: NULL buffer");
+    PROF_LAUNCH(gab::k_landmarks_bwd, dim3((V + 255) / 256), dim3(256), 0, st, V, F, L, faces, is64, lmk_face, lmk_bary, lmk_order, vert_begin,
+                       d_landmarks, d_verts, accumulate);
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_landmarks_bwd failed");
+    return GAB_OK;
+}
+
+int gab_root_joint(const GabRig* rig_, const float* v_shaped, float* root, void* stream_)
+{
+    gab::Rig rig;
+    if (int rc = to_rig(rig_, &rig)) return rc;
+    if (!v_shaped || !root) return fail(GAB_E_ARG, "gab_root_joint: NULL buffer");
+    PROF_LAUNCH(gab::k_root_joint, dim3(1), dim3(1024), 0, (hipStream_t)stream_, rig, v_shaped, root);
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_root_joint failed");
+    return GAB_OK;
+}
+
+int gab_root_center(int32_t V, const float* verts, const float* root, const float* translation, float* out, void* stream_)
+{
+    if (V <= 0 || V > (1 << 28)) return fail(GAB_E_ARG, "gab_root_center: bad sizes");
+    if (!verts || !root || !translation || !out) return fail(GAB_E_ARG, "gab_root_center: NULL buffer");
+    PROF_LAUNCH(gab::k_root_center, dim3((3 * V + 255) / 256), dim3(256), 0, (hipStream_t)stream_, 3 * V, verts, root, translation, out);
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_root_center failed");
+    return GAB_OK;
+}
+
+int gab_root_center_backward(const GabRig* rig_, const float* d_out, float* d_v_shaped, float* d_translation, void* stream_)
+{
+    gab::Rig rig;
+    if (int rc = to_rig(rig_, &rig)) return rc;
+    if (!d_out || !d_v_shaped) return fail(GAB_E_ARG, "gab_root_center_backward: NULL buffer");
+    PROF_LAUNCH(gab::k_root_center_bwd, dim3(1), dim3(1024), 0, (hipStream_t)stream_, rig, d_out, d_v_shaped, d_translation);
+    LAUNCH_CHECK(GAB_E_HIP, "launch of k_root_center_bwd failed");
     return GAB_OK;
 }
 

@@ -286,16 +286,39 @@ class FlameHead(nn.Module):
         self.n_shape_params = 300
         self.n_expr_params = self.shapedirs.shape[2] - 300
         self.impl = impl
+        if "full_lmk_faces_idx" in rig and "full_lmk_bary_coords" in rig:
+            self.attach_landmarks(rig["full_lmk_faces_idx"], rig["full_lmk_bary_coords"])
+
+    def attach_landmarks(self, lmk_faces_idx, lmk_bary_coords):
+        """The landmark embedding of flame.py:131-143 (landmark_embedding_with_eyes.npy: `full_lmk_faces_idx`, `full_lmk_bary_coords`), as
+        (L,) / (L,3) or in the reference's (1,L) / (1,L,3): checked against `faces` here, on the host, once, and registered as the two
+        buffers the reference registers -- (L,) long and (L,3) fp32."""
+        from .binding import check_landmark_embedding
+
+        idx, bary = check_landmark_embedding(self.faces, lmk_faces_idx, lmk_bary_coords)
+        dev = self.faces.device
+        self.register_buffer("full_lmk_faces_idx", idx.to(dev))
+        self.register_buffer("full_lmk_bary_coords", bary.to(dev))
+        return self
 
     def forward(self, shape, expr, rotation, neck, jaw, eyes, translation, zero_centered_at_root_node=False,
                 return_landmarks=True, return_verts_cano=False, static_offset=None, dynamic_offset=None):
-        if zero_centered_at_root_node or return_landmarks:
-            raise NotImplementedError("only the per-frame path of GaussianAvatars is mirrored "
-                                      "(zero_centered_at_root_node=False, return_landmarks=False)")
         rig = dict(v_template=self.v_template, shapedirs=self.shapedirs, posedirs=self.posedirs,
                    J_regressor=self.J_regressor, lbs_weights=self.lbs_weights, parents=self.parents)
-        verts, v_shaped = unfused.flame_forward(rig, shape, expr, rotation, neck, jaw, eyes, translation, static_offset)
-        return [verts, v_shaped] if return_verts_cano else verts
+        if not (zero_centered_at_root_node or return_landmarks):   # the per-frame call of GaussianAvatars
+            verts, v_shaped = unfused.flame_forward(rig, shape, expr, rotation, neck, jaw, eyes, translation, static_offset)
+            return [verts, v_shaped] if return_verts_cano else verts
+        if return_landmarks and getattr(self, "full_lmk_faces_idx", None) is None:
+            raise ValueError("return_landmarks=True (the default) needs a landmark embedding: call attach_landmarks(lmk_faces_idx, "
+                             "lmk_bary_coords) first, or pass return_landmarks=False")
+        verts, v_shaped = unfused.flame_forward(rig, shape, expr, rotation, neck, jaw, eyes, translation, static_offset,
+                                                zero_centered_at_root_node=zero_centered_at_root_node)
+        ret = [verts]                                               # flame.py:539-558: [vertices, (v_shaped), (landmarks)]
+        if return_verts_cano:
+            ret.append(v_shaped)
+        if return_landmarks:
+            ret.append(unfused.landmarks(verts, self.faces, self.full_lmk_faces_idx, self.full_lmk_bary_coords))
+        return ret if len(ret) > 1 else ret[0]
 
 
 class FlameGaussianModel(GaussianModel):
@@ -338,8 +361,10 @@ class FlameGaussianModel(GaussianModel):
         self.num_timesteps = fp["expr"].shape[0]
 
     def load_ply(self, path, device="cuda", spatial_sort: Optional[bool] = None, **kwargs):
-        """scene/flame_gaussian_model.py:229-237: the PLY plus the flame_param.npz stored next to it.  `spatial_sort`: as GaussianModel.load_ply
-        (default on), by the template centre of each splat's face."""
+        """scene/flame_gaussian_model.py:226-269: the PLY plus the flame_param.npz stored next to it.  `spatial_sort`: as GaussianModel.load_ply
+        (default on), by the template centre of each splat's face.  `motion_path` (:239-258): an npz whose seven per-timestep entries replace
+        the dynamic FLAME parameters, `shape` and `static_offset` staying.  `disable_fid` (:260-269): the splats bound to the listed faces are
+        dropped -- from the leaves and the binding like the reference, and from everything else that has a row per splat."""
         import os
 
         from . import io as gio
@@ -349,6 +374,28 @@ class FlameGaussianModel(GaussianModel):
         super().load_ply(path, device=device, spatial_sort=spatial_sort, face_centers=template_face_centers(self) if spatial_sort else None)
         if not kwargs.get("has_target", False):
             self.load_flame_param(gio.load_flame_param(os.path.join(os.path.dirname(str(path)), "flame_param.npz")), device=device)
+        if kwargs.get("motion_path") is not None:
+            motion = gio.load_flame_param(str(kwargs["motion_path"]))
+            fp = {k: self.flame_param[k] for k in ("shape", "static_offset")}
+            for k in ("translation", "rotation", "neck_pose", "jaw_pose", "eyes_pose", "expr", "dynamic_offset"):
+                fp[k] = torch.as_tensor(motion[k], dtype=torch.float32, device=device)
+            self.flame_param = fp
+            self.num_timesteps = fp["expr"].shape[0]
+        disable_fid = kwargs.get("disable_fid")
+        if disable_fid is not None and len(disable_fid) > 0:
+            fid = torch.as_tensor(disable_fid, device=self.binding.device).reshape(-1).to(self.binding.dtype)
+            keep = (self.binding[:, None] != fid[None, :]).all(-1)
+            n = keep.shape[0]
+            for attr in ("_xyz", "_features_dc", "_features_rest", "_scaling", "_rotation", "_opacity"):
+                p = getattr(self, attr)
+                setattr(self, attr, nn.Parameter(p.detach()[keep].contiguous().requires_grad_(p.requires_grad)))
+            self.binding = self.binding[keep]
+            self.binding_counter = torch.bincount(self.binding.long(), minlength=self.binding_counter.shape[0]).to(self.binding_counter.dtype)
+            # what prune_points keeps in step with the leaves (densify.prune_points), and the file-row permutation of the spatial order
+            self.xyz_gradient_accum, self.denom, self.max_radii2D = self.xyz_gradient_accum[keep], self.denom[keep], self.max_radii2D[keep]
+            order = getattr(self, "_gaa_order", None)
+            if isinstance(order, torch.Tensor):
+                self._gaa_order = order[keep.to(order.device)] if order.shape[0] == n else None
 
     def save_ply(self, path):
         """scene/flame_gaussian_model.py:219-224"""

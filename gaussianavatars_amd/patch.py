@@ -168,6 +168,11 @@ def _prepared(head):
     return head
 
 
+def _device_f32(head, *tensors) -> bool:
+    """Device fp32 throughout (what the landmark / root-centring kernels take; anything else is the composed-torch statement's)."""
+    return head.v_template.is_cuda and all(t is None or (t.is_cuda and t.dtype is torch.float32) for t in tensors)
+
+
 def _make_flame_forward(cls):
     orig = _ORIG[(cls, "forward")]
 
@@ -175,6 +180,12 @@ def _make_flame_forward(cls):
                 return_landmarks=True, return_verts_cano=False, static_offset=None, dynamic_offset=None):
         fusable = (getattr(self, "impl", _default_impl()) != "unfused" and not zero_centered_at_root_node and not return_landmarks
                    and shape.shape[0] == 1)
+        if (not fusable and (zero_centered_at_root_node or return_landmarks) and getattr(self, "impl", _default_impl()) != "unfused"
+                and shape.shape[0] == 1 and (not return_landmarks or getattr(self, "full_lmk_faces_idx", None) is not None)
+                and _device_f32(self, shape, expr, rotation, neck, jaw, eyes, translation, static_offset)):
+            # the two other switches (flame.py:532-553) on the kernels: include/gab_landmarks.h
+            return fused.flame_head_outputs(_prepared(self), shape, expr, rotation, neck, jaw, eyes, translation, static_offset,
+                                            zero_centered_at_root_node, return_landmarks, return_verts_cano)
         if not fusable:
             kw = dict(zero_centered_at_root_node=zero_centered_at_root_node, return_landmarks=return_landmarks,
                       return_verts_cano=return_verts_cano, static_offset=static_offset, dynamic_offset=dynamic_offset)

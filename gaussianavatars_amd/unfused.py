@@ -72,9 +72,10 @@ def rodrigues(rot_vecs):
     return eye + s * K + (1 - c) * torch.bmm(K, K)
 
 
-def flame_forward(rig, shape, expr, rotation, neck, jaw, eyes, translation, static_offset=None):
+def flame_forward(rig, shape, expr, rotation, neck, jaw, eyes, translation, static_offset=None, zero_centered_at_root_node=False):
     """rig: dict of buffers (v_template (V,3), shapedirs (V,3,400), posedirs (36,3V), J_regressor (5,V),
-    lbs_weights (V,5), parents).  Batch-1 inputs shaped like the reference's.  -> (verts, v_shaped)."""
+    lbs_weights (V,5), parents).  Batch-1 inputs shaped like the reference's.  -> (verts, v_shaped).
+    zero_centered_at_root_node: flame.py:532-534, the posed root joint is subtracted before the translation is added."""
     B = shape.shape[0]
     betas = torch.cat([shape, expr], 1)
     pose = torch.cat([rotation, neck, jaw, eyes], 1)
@@ -100,7 +101,16 @@ def flame_forward(rig, shape, expr, rotation, neck, jaw, eyes, translation, stat
     T = (rig["lbs_weights"][None] @ A.view(B, nj, 16)).view(B, -1, 4, 4)
     vh = F.pad(v_posed, [0, 1], value=1.0)
     verts = (T @ vh[..., None])[:, :, :3, 0]
+    if zero_centered_at_root_node:
+        verts = verts - G[:, [0], :3, 3]   # the posed joints are the chain's translation columns (lbs.py:296); the root's is J[:, 0] itself
     return verts + translation[:, None, :], v_shaped
+
+
+def landmarks(verts, faces, lmk_faces_idx, lmk_bary_coords):
+    """vertices2landmarks (flame_model/lbs.py:86-97): verts (B,V,3), faces (F,3), lmk_faces_idx (L,), lmk_bary_coords (L,3) -> (B,L,3)."""
+    lmk_faces = torch.index_select(faces, 0, lmk_faces_idx.reshape(-1).long())   # (L,3) vertex indices
+    lmk_vertices = verts[:, lmk_faces.long()]                                      # (B,L,3 corners,3)
+    return torch.einsum("blfi,lf->bli", lmk_vertices, lmk_bary_coords.reshape(-1, 3).to(verts.dtype))
 
 
 # ---- per-face frames -------------------------------------------------------------------------
